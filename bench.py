@@ -9,25 +9,32 @@ sigma_sys = 1 mag): theta[B, 6] resident in HBM -> logL[B] in HBM.  With N > 1 e
 evaluates its own 4096-point shard (no data-path collective inside the evaluation) and the
 shards' logL are exchanged with ONE RCCL all-gather per step (weak scaling).
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the K steps, writes what the last
+timed step computed (``--dump-outputs DIR``: rank 0's logL as ``DIR/logL.npy``, float64; the inputs are seeded, so two builds can be
+compared output for output) and prints the line.  ``--full`` adds every other leg described below: `value_cold`, `sustained`,
+`host_call_ms`, `device_walk`, `device_walk_queue`, the CPU baselines, and with N > 1 `other_scaling`, `device_walk_queue_sharded`
+and the kernel time of `roofline` beside a captured graph.
 
 Without a launcher (RANK unset) and N > 1 the script starts ``torch.distributed.run`` itself as a CHILD process --
 before anything here touches the GPU -- and relays the child's JSON line.  ``--scaling weak`` (default) keeps 4096
 live points per GPU; ``--scaling strong`` splits ONE 4096-point batch over the ranks (north_star's 8-GPU target).
 
 Before the W warmup steps ``--clock-warmup-steps`` (1536) untimed steps let the GPU's clocks settle (a fresh process runs its first
-~900 launches at ramping clocks).  The K-step region (W untimed steps first, each region bracketed by barrier + synchronize) is timed ``--repeats`` times and
+~900 launches at ramping clocks).  The K-step region (W untimed steps first, each region bracketed by barrier + synchronize) is timed ``--repeats`` times
+(fewer where K is so large that they would take more than 5 s together; the line's `repeats` is the count) and
 `value` / `ms_per_step` are the MEDIAN region's (`spread_pct` = the 10-90 percentile spread over the repeats, relative to it).
 With N > 1 over RCCL the K steps of a timed region -- evaluation on one stream, the all-gather of the previous step's log L on a second --
 are replayed as ONE captured HIP graph (issued step by step the pipeline's event calls cost the host more than the kernel they overlap with;
 NMMA_BENCH_NO_GRAPH=1 keeps the stream form, NMMA_BENCH_BLOCKING=1 one stream).
-With N > 1 BOTH scaling modes are measured in the one invocation: the line's top level is the mode ``--scaling`` names, the
+With N > 1 and ``--full`` BOTH scaling modes are measured in the one invocation: the line's top level is the mode ``--scaling`` names, the
 other one sits under ``other_scaling``.  Rank 0 prints ONE JSON line.  `roofline` prices the log-likelihood kernel (em_logl: surrogate
 MLP on the f32 MFMA pipe, SVD reconstruction, interpolation and likelihood terms in one launch)
 against the dense fp32 MFMA peak with the ALGORITHMIC flop count of SURVEY.md section 8d
 (sum over filters of 2*NP*NH + 2*NH*NC + 2*NC*NT = 369 384 flop/eval); its duration is
-measured with HIP events on the launch stream inside the timed region.  `cpu_baseline`
+measured with HIP events on the launch stream inside the timed region.  `cpu_baseline` (``--full``)
 times the CPU oracle (a port of the reference's per-sample Python calling pattern,
 scipy.stats included) on one host core over a bounded sample of the same workload.
 """
@@ -44,6 +51,8 @@ if ROOT not in sys.path:
 PEAK_FP32_MFMA_TFLOPS = 157.3   # /opt/skills/guides/MI355X_MICROARCH.md, dense f32 MFMA
 BATCH_PER_GPU = 4096
 N_THETA_SETS = 8
+MAX_EVENT_PAIRS = 4096          # HIP event pairs a timed region may record for `roofline` (created up front: a long --steps must not pay for millions)
+REGION_BUDGET_S = 5.0           # the repeats of the timed region stop where their total would pass this (a long --steps is timed once)
 
 
 def _profiled_traffic():
@@ -82,7 +91,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=25, help="the K-step region is timed this many times; value = the median region")
+    ap.add_argument("--repeats", type=int, default=25,
+                    help="the K-step region is timed this many times (fewer when they would not fit into "
+                         f"{REGION_BUDGET_S:g} s, never less than once); value = the median region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything around the headline figure: the cold region, the sustained leg, host calls, the device walk "
+                         "and the sampler queue, the CPU baselines; with N > 1 the other scaling mode and the sharded queue")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (rank 0's logL) as DIR/logL.npy")
     ap.add_argument("--clock-warmup-steps", type=int, default=1536,
                     help="untimed steps BEFORE the W warmup steps: the GPU's clocks need ~30 ms of continuous load (~900 launches) to settle")
     ap.add_argument("--sustained-seconds", type=float, default=5.0,
@@ -142,6 +158,12 @@ def main():
     dev = torch.device(f"cuda:{local_rank}")
     import gc
 
+    def max_over_ranks(values):
+        """Elementwise MAX over the ranks of a list of seconds (gloo is given host tensors)."""
+        t = torch.tensor(values, dtype=torch.float64, device="cpu" if share_gpu else dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return t.cpu().tolist()
+
     def measure(scaling, cold=False):
         """W untimed + K timed steps of one scaling mode: (elapsed max over ranks, rows of this rank, global batch, pipelined, prof).
         cold: FIRST time one contract-shaped region -- W warm-up steps, K timed steps, nothing before them -- as the process's first
@@ -176,18 +198,20 @@ def main():
             torch.cuda.synchronize()
             torch.cuda.set_stream(s_coll)            # torch.distributed enqueues on the current stream
 
-        def step(i):
+        def step(i, k=None):
+            """Step number i of this process (the pipelined form alternates its buffers on it) on theta set k (default: i)."""
+            theta = thetas[(i if k is None else k) % N_THETA_SETS]
             if pipelined:
                 b = i & 1
                 if i >= 2:
                     s_eval.wait_event(ev_coll[b])    # the gather that read outs[b] two steps ago
-                eng.loglike(thetas[i % N_THETA_SETS], out=outs[b], stream=s_eval)
+                eng.loglike(theta, out=outs[b], stream=s_eval)
                 ev_eval[b].record(s_eval)
                 s_coll.wait_event(ev_eval[b])
                 dist.all_gather_into_tensor(gathers[b], outs[b])
                 ev_coll[b].record(s_coll)
                 return
-            eng.loglike(thetas[i % N_THETA_SETS], out=out)
+            eng.loglike(theta, out=out)
             if use_dist:
                 if share_gpu:
                     send[:B] = out
@@ -226,9 +250,7 @@ def main():
             cold_elapsed = time.perf_counter() - t0
             done += args.steps
             if use_dist:
-                t = torch.tensor([cold_elapsed], dtype=torch.float64, device=dev)
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-                cold_elapsed = float(t.item())
+                cold_elapsed = max_over_ranks([cold_elapsed])[0]
         # N > 1, pipelined: the K steps of a timed region as ONE captured HIP graph.  Issued step by step the two-stream pipeline costs
         # the HOST 38 us per step -- four event record / wait calls at ~5.5 us each on top of the kernel launch (5.4 us) and the
         # collective's call (10.5 us): tools/experiments/step_cost_probe.py -- i.e. more than the 27.6 us kernel it is meant to overlap
@@ -282,13 +304,14 @@ def main():
                 graph, graph_note = None, "another rank could not capture its graph"
 
         def region():
-            """K steps: one graph launch, or K stream-ordered steps."""
+            """K steps: one graph launch, or K stream-ordered steps.  Every region walks the theta sets from set 0, as the captured
+            graph does: what its last step computes does not depend on how many regions were timed."""
             nonlocal done
             if graph is not None:
                 graph.replay()
             else:
-                for i in range(done, done + args.steps):
-                    step(i)
+                for k in range(args.steps):
+                    step(done + k, k)
             done += args.steps
 
         n_before_clock = done
@@ -313,13 +336,15 @@ def main():
         # The K-step region is timed R times (each one bracketed by barrier + synchronize on both sides); `value` comes from
         # the MEDIAN region: at the driver's flags the region is well under a millisecond and a single one carries the noise
         # of whatever the box did in that millisecond.
-        times, prof = [], dict(fused_ms_total=0.0, n_launches=0)
-        for _ in range(args.repeats):
+        # (at most --repeats regions, as many as fit into REGION_BUDGET_S by the first one's time -- the max over the ranks, so that
+        #  every rank times the same number: 25 regions at the default K, one where K makes a region last seconds)
+        times, prof, n_repeats = [], dict(fused_ms_total=0.0, n_launches=0), max(1, args.repeats)
+        while len(times) < n_repeats:
             if use_dist:
                 dist.barrier()
             torch.cuda.synchronize()
             if graph is None:
-                eng.profile_begin(args.steps)
+                eng.profile_begin(min(args.steps, MAX_EVENT_PAIRS))
             t0 = time.perf_counter()
             region()
             torch.cuda.synchronize()
@@ -331,7 +356,10 @@ def main():
                 p = eng.profile_end()
                 prof["fused_ms_total"] += p["fused_ms_total"]
                 prof["n_launches"] += p["n_launches"]
-        if graph is not None:
+            if len(times) == 1:
+                first = max_over_ranks(times)[0] if use_dist else times[0]
+                n_repeats = max(1, min(n_repeats, int(REGION_BUDGET_S / first)))
+        if graph is not None and args.full:
             # (HIP events cannot bracket launches inside a captured graph: the kernel time of `roofline` comes from the same K steps
             #  issued stream by stream right after the timed regions -- same kernels, same collectives beside them; the line says so)
             for _ in range(min(args.repeats, 5)):
@@ -349,9 +377,7 @@ def main():
         if pipelined:
             torch.cuda.set_stream(prev_stream)
         if use_dist:        # every region's time is the MAX over ranks
-            t = torch.tensor(times, dtype=torch.float64, device=dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            times = t.cpu().tolist()
+            times = max_over_ranks(times)
         elapsed = float(np.median(times))
         spread = 100.0 * (float(np.percentile(times, 90)) - float(np.percentile(times, 10))) / elapsed if len(times) > 1 else 0.0
         n_done = args.steps if graph is not None else done      # (the profiling leg's steps count from 0)
@@ -362,7 +388,7 @@ def main():
             assert np.all(np.isfinite(glast)) and np.all(glast < 0)
         assert np.all(np.isfinite(last)) and np.all(last < 0)
         return dict(elapsed=elapsed, B=B, global_batch=global_batch, pipelined=pipelined, graph=graph is not None, graph_note=graph_note, prof=prof,
-                    geom=eng.last_launch_geometry(), n_clock=n_clock,
+                    geom=eng.last_launch_geometry(), n_clock=n_clock, repeats=len(times), last=glast if graph is not None else last,
                     spread_pct=spread, best=min(times), worst=max(times), cold_elapsed=cold_elapsed, thetas=thetas, out=out)
 
     def exchange_label(m):
@@ -374,14 +400,15 @@ def main():
                 + (", the K steps of a region replayed as ONE captured HIP graph (kernel time of `roofline`: the same steps issued stream by stream)"
                    if m.get("graph") else (f" (graph capture failed: {m['graph_note']})" if m.get("graph_note") else "")))
 
-    main_mode = measure(args.scaling, cold=True)
-    # with more than one GPU the other scaling mode is measured in the same invocation and reported under "other_scaling"
-    other = measure("strong" if args.scaling == "weak" else "weak") if world > 1 else None
+    # a plain run: set-up, clock warm-up, W + K steps, the line.  Everything else the benchmark measures waits for --full
+    main_mode = measure(args.scaling, cold=args.full)
+    # --full with more than one GPU: the other scaling mode is measured in the same invocation and reported under "other_scaling"
+    other = measure("strong" if args.scaling == "weak" else "weak") if args.full and world > 1 else None
 
     # the sampler queue sharded over the ranks (parallel.ShardedQueue: what the reference's task farm does with a queue's chains,
     # core/mpi_setup.py:651-667, :679-683) -- every rank takes part, rank 0 reports; context, never `value`
     sharded = None
-    if use_dist:
+    if args.full and use_dist:
         try:
             sharded = device_walk_queue_sharded(eng, case, syn, dist, world, rank, dev, share_gpu)
         except Exception as exc:      # noqa: BLE001  (a failure here must not cost the contract line; every rank fails alike or the barrier below reports)
@@ -398,11 +425,10 @@ def main():
             "value": evals / m["elapsed"], "unit": "evals/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * m["elapsed"] / args.steps,
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32 MLP + f64",
-            "data": "synthetic", "repeats": args.repeats, "spread_pct": m["spread_pct"], "clock_warmup_launches": m["n_clock"],
-            # the contract-shaped single region (W warm-up steps, K timed steps) run as the process's FIRST load, before the clock warm-up
-            "value_cold": evals / m["cold_elapsed"], "ms_per_step_cold": 1e3 * m["cold_elapsed"] / args.steps,
-            "value_is": f"steady state: median of {args.repeats} timed K-step regions after {m['n_clock']} untimed clock-warm-up steps + W; "
-                        "value_cold is the single W + K region of a fresh process; sustained.evals_per_s is >= 5 s of back-to-back steps",
+            "data": "synthetic", "repeats": m["repeats"], "spread_pct": m["spread_pct"], "clock_warmup_launches": m["n_clock"],
+            "value_is": f"steady state: median of {m['repeats']} timed K-step regions after {m['n_clock']} untimed clock-warm-up steps + W"
+                        + ("; value_cold is the single W + K region of a fresh process; sustained.evals_per_s is >= 5 s of back-to-back steps"
+                           if args.full else " (--full adds the legs around it)"),
             "ms_per_step_best": 1e3 * m["best"] / args.steps, "ms_per_step_worst": 1e3 * m["worst"] / args.steps,
             "config": {"workload": "BASELINE config 2: Bu2019lm SVD surrogate (NP=4, NH=2048, NC=10, NT=211), "
                                    "AT2017gfo 6-filter synthetic photometry (99 epochs, 1 upper limit), "
@@ -416,6 +442,12 @@ def main():
                          "kernel_launches_timed": prof["n_launches"], "flops_per_eval": eng.flops_per_eval,
                          "traffic_unit": "bytes/launch (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE)"},
         }
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "logL.npy"), np.asarray(m["last"], dtype=np.float64))
+        if args.full:
+            # the contract-shaped single region (W warm-up steps, K timed steps) run as the process's FIRST load, before the clock warm-up
+            line["value_cold"], line["ms_per_step_cold"] = evals / m["cold_elapsed"], 1e3 * m["cold_elapsed"] / args.steps
         if other is not None:
             o_scaling = "strong" if args.scaling == "weak" else "weak"
             o_ms = other["prof"]["fused_ms_total"] / max(1, other["prof"]["n_launches"])
@@ -425,12 +457,12 @@ def main():
                                      "exchange": exchange_label(other), "kernel_ms": o_ms}
         if sharded is not None:
             line["device_walk_queue_sharded"] = sharded
-        if world == 1 and args.sustained_seconds > 0:
+        if args.full and world == 1 and args.sustained_seconds > 0:
             try:
                 line["sustained"] = sustained_leg(eng, m["thetas"], m["out"], B, args.sustained_seconds, line["value"], fused_ms)
             except Exception as exc:      # noqa: BLE001
                 line["sustained"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if not args.no_cpu_baseline and world == 1:      # (the profiled command lines pass --no-cpu-baseline: device launches only)
+        if args.full and not args.no_cpu_baseline and world == 1:      # (--no-cpu-baseline leaves these legs out of a --full run)
             # (context blocks: a failure in one of them must not cost the contract line)
             def context(key, fn):
                 try:

@@ -27,7 +27,7 @@ def _bench(*flags, **env_extra):
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_two_ranks_both_scaling_modes(scaling):
-    line = _bench("--gpus", "2", "--scaling", scaling)
+    line = _bench("--gpus", "2", "--scaling", scaling, "--full")         # (--full: the other scaling mode is measured too)
     assert line["n_gpus"] == 2 and line["steps"] == 5 and line["warmup"] == 2 and line["scaling"] == scaling
     assert line["metric"].startswith("log-likelihood evals/sec") and line["unit"] == "evals/s" and line["higher_is_better"] is True
     want = {"weak": (4096, 8192), "strong": (2048, 4096)}
@@ -62,7 +62,8 @@ def test_bench_rccl_exchange_with_one_rank(blocking):
     after every evaluation -- on a second stream, overlapping the next kernel (the form an 8-GPU run takes), and blocking on the
     compute stream -- plus the barrier / max-over-ranks timing.  No scaling number; the code an N-GPU run executes has run."""
     # ("stream": the two-stream pipeline issued step by step; "0": the same K steps of a region replayed as one captured HIP graph)
-    line = _bench("--gpus", "1", "--repeats", "3", NMMA_BENCH_SHARE_GPU="0", NMMA_BENCH_FORCE_DIST="1", NMMA_BENCH_BLOCKING="1" if blocking == "1" else "0",
+    # (--full: beside a captured graph the kernel time of `roofline` takes a leg of its own)
+    line = _bench("--gpus", "1", "--repeats", "3", "--full", NMMA_BENCH_SHARE_GPU="0", NMMA_BENCH_FORCE_DIST="1", NMMA_BENCH_BLOCKING="1" if blocking == "1" else "0",
                   NMMA_BENCH_NO_GRAPH="1" if blocking == "stream" else "0",
                   HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     assert line["n_gpus"] == 1 and line["steps"] == 5 and line["warmup"] == 2 and line["repeats"] == 3
@@ -78,6 +79,28 @@ def test_bench_line_reports_the_median_region():
     line = _bench("--repeats", "7")
     assert line["repeats"] == 7 and line["spread_pct"] >= 0
     assert line["ms_per_step_best"] <= line["ms_per_step"] <= line["ms_per_step_worst"]
+
+
+def test_plain_run_is_lean_and_dumps_what_its_last_step_computed(tmp_path):
+    """Without --full the line carries the headline figure and none of the legs around it; --dump-outputs writes the logL of the last
+    timed step: step K - 1 of a region evaluates theta set (K - 1) % 8, seeded, so the file is the same from run to run."""
+    import torch
+    from nmma_amd import synthetic as syn
+    from nmma_amd.engine import EMEngine
+    line = _bench("--steps", "13", "--repeats", "2", "--dump-outputs", str(tmp_path / "out"))
+    assert line["steps"] == 13 and line["repeats"] == 2 and line["value"] == pytest.approx(4096 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    for key in ("value_cold", "sustained", "host_call_ms", "device_walk", "device_walk_queue", "cpu_baseline", "cpu_baseline_all_cores",
+                "other_scaling", "device_walk_queue_sharded"):
+        assert key not in line, key
+    assert [p.name for p in (tmp_path / "out").iterdir()] == ["logL.npy"]
+    got = np.load(tmp_path / "out" / "logL.npy")
+    assert got.dtype == np.float64 and got.shape == (4096,)
+    case = syn.config2_case()
+    eng = EMEngine.from_case(case)
+    theta = syn.draw_theta(1000 + (13 - 1) % 8, 4096, case["names"])[1]
+    want = eng.loglike(torch.as_tensor(theta, device="cuda:0")).cpu().numpy()
+    eng.close()
+    assert np.array_equal(got, want)
 
 
 def test_multi_device_evaluator_in_one_process():

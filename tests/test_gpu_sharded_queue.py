@@ -46,10 +46,10 @@ def test_sharded_queue_ranks_sharing_the_gpu_reproduce_the_single_device_queue(w
 
 
 def test_bench_two_ranks_prints_the_sharded_queue_block():
-    """``bench.py --gpus 2`` (ranks sharing the GPU, gloo): the N > 1 line carries ``device_walk_queue_sharded`` -- weak and strong."""
+    """``bench.py --full --gpus 2`` (ranks sharing the GPU, gloo): the N > 1 line carries ``device_walk_queue_sharded`` -- weak and strong."""
     import json
     env = dict(_env(), NMMA_BENCH_SHARE_GPU="1")
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--repeats", "3",
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "5", "--warmup", "2", "--repeats", "3",
                            "--clock-warmup-steps", "64", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
@@ -65,7 +65,7 @@ def test_bench_two_ranks_prints_the_sharded_queue_block():
 def test_bench_one_rank_over_rccl_prints_the_sharded_queue_block():
     import json
     env = dict(_env(), NMMA_BENCH_FORCE_DIST="1")
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--repeats", "3",
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "5", "--warmup", "2", "--repeats", "3",
                            "--clock-warmup-steps", "64", "--no-cpu-baseline", "--sustained-seconds", "0"], capture_output=True, text=True, timeout=900,
                           env=env, cwd=ROOT)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]

@@ -241,10 +241,9 @@ def test_photometry_reader(tmp_path):
     assert times["ps1::g"][0] == pytest.approx(0.5)
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/example_files/lightcurves/AT2017gfo.dat"),
-                    reason="reference example data not available")
 def test_reads_reference_example_photometry():
-    d = em_io.load_em_observations("/root/reference/example_files/lightcurves/AT2017gfo.dat")
+    # (tests/golden/AT2017gfo.dat: the reference's example_files/lightcurves/AT2017gfo.dat, byte for byte)
+    d = em_io.load_em_observations(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "AT2017gfo.dat"))
     assert {k: len(v["time"]) for k, v in d.items()}["ps1::g"] == 13
     assert sum(len(v["time"]) for v in d.values()) == 141
     assert sum(np.isinf(v["mag_error"]).sum() for v in d.values()) == 3

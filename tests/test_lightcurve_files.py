@@ -100,9 +100,9 @@ def test_round_trips(tmp_path):
     np.testing.assert_allclose(back["g"]["mag_error"], [0.1, 0.1, 0.1])
 
 
-@pytest.mark.skipif(not os.path.isfile("/root/reference/example_files/lightcurves/AT2017gfo.dat"), reason="the reference tree is not here")
 def test_the_reference_example_file():
-    data = load_em_observations("/root/reference/example_files/lightcurves/AT2017gfo.dat")
+    # (tests/golden/AT2017gfo.dat: the reference's example photometry, example_files/lightcurves/AT2017gfo.dat, byte for byte)
+    data = load_em_observations(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "AT2017gfo.dat"))
     assert sum(len(v["time"]) for v in data.values()) == 141 and len(data) == 9
     assert sum(int(np.isinf(v["mag_error"]).sum()) for v in data.values()) == 3
     assert all(np.all(np.diff(v["time"]) >= 0) for v in data.values())

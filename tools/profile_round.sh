@@ -11,8 +11,8 @@ tag=${1:-r03}
 o=gpurun_out/$tag
 rm -rf $o; mkdir -p $o
 export TMPDIR=/tmp
-python3 bench.py --steps 200 --warmup 20 > $o/bench_line.json 2> $o/bench.err
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $o/bench_line_driver_flags.json 2> $o/bench_driver.err     # what the driver runs
+python3 bench.py --full --steps 200 --warmup 20 > $o/bench_line.json 2> $o/bench.err
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $o/bench_line_driver_flags.json 2> $o/bench_driver.err     # what the driver runs
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_bench -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --sustained-seconds 0 > $o/stats_bench.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/stats_dt05 -- python3 tools/perf_case.py c2_dt05_limit 4096 > $o/stats_dt05.log 2>&1
 export NMMA_EM_NO_LEAN_LIM=1       # the same case on the extended task (em_logl<.., 2>), which had the finite limits before
@@ -56,5 +56,5 @@ rocprofv3 --pmc SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_V
 find $o -name "*kernel_stats.csv" | head
 cat $o/bench_line.json
 # the sampler queue (4096 records x 100 steps): kernel times of the fused MCMC step and of the queue's other launches
-bash tools/gpu_fuse_prof.sh > $o/stats_queue.log 2>&1
-cp $(find gpurun_out/prof_fuse/a -name "*kernel_stats.csv" | head -1) $o/queue_kernel_stats.csv 2>/dev/null
+bash tools/gpu_fuse_prof.sh $o/prof_fuse > $o/stats_queue.log 2>&1
+cp $(find $o/prof_fuse/a -name "*kernel_stats.csv" | head -1) $o/queue_kernel_stats.csv 2>/dev/null
