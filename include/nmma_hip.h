@@ -580,6 +580,53 @@ int32_t nmma_em_debug_timeline(nmma_em_handle* h, const double* theta_dev, int64
 
 /* HIP-event timing of the dominant kernel on the launch stream: between begin and end
  * every nmma_em_loglike call brackets its fused per-filter kernel with two events. */
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Gaussian-process surrogate of the SVD model (interpolation_type "sklearn_gp": nmma/em/lightcurve_generation.py:199-211, trained by
+ * nmma/em/training.py:429-453 as ConstantKernel x RationalQuadratic with a scalar length scale).  An object of its own next to an
+ * nmma_em_handle of kind NMMA_MODEL_EXTERNAL, which supplies the theta layout (model_param slots) and sample_times and takes the
+ * curves in nmma_em_loglike_lc / nmma_em_lightcurves_lc.  For filter m, coefficient i and x = (theta_model - param_mins) /
+ * (param_maxs - param_mins), all in fp64 without contraction:
+ *     d2_n = sum_p (x_p - X[n][p])^2;  k_n = constant_i * (1 + d2_n / (2 rq_alpha_i length_scale_i^2)) ** (-rq_alpha_i)
+ *     c[i] = y_std_i * (sum_n k_n alpha[i][n]) + y_mean_i
+ * Filters may have training sets of different sizes: X and alpha are the filters' arrays one after the other. */
+typedef struct nmma_gp_config {
+    int32_t abi_version, device;
+    int32_t n_model_filters, n_params, n_coeff, n_tt;
+    const int32_t* n_train;        /* [M] training points N_m of every filter */
+    const double* X;               /* filter m: [N_m][NP]  gp.X_train_ (the same for every coefficient of a filter) */
+    const double* alpha;           /* filter m: [NC][N_m]  gp.alpha_ */
+    const double* constant;        /* [M][NC] kernel_.k1.constant_value */
+    const double* length_scale;    /* [M][NC] kernel_.k2.length_scale */
+    const double* rq_alpha;        /* [M][NC] kernel_.k2.alpha */
+    const double* y_mean;          /* [M][NC] _y_train_mean */
+    const double* y_std;           /* [M][NC] _y_train_std */
+    const double* VA;              /* [M][NT][NC] */
+    const double* mins;            /* [M][NT] */
+    const double* maxs;            /* [M][NT] */
+    const double* tt;              /* [M][NT] */
+    const double* param_mins;      /* [M][NP] */
+    const double* param_maxs;      /* [M][NP] */
+} nmma_gp_config;
+
+typedef struct nmma_gp_handle nmma_gp_handle;
+int32_t nmma_gp_create(const nmma_gp_config* cfg, nmma_gp_handle** out);
+void nmma_gp_destroy(nmma_gp_handle* gp);
+
+/* coeff_dev[B][M][NC] fp64: the surrogate stage alone (B x M x NC calls of gp.predict).  em: a handle with gp's n_params on gp's device. */
+int32_t nmma_gp_coefficients(nmma_gp_handle* gp, nmma_em_handle* em, const double* theta_dev, int64_t B, int64_t ld, double* coeff_dev,
+                             void* stream);
+/* lc_dev[B][M][NS]: source-frame absolute magnitudes on em's sample_times, +inf outside tt (calc_svd_lc with extrapolate = inf,
+ * lightcurve_generation.py:174-177); em must list gp's n_model_filters.  One launch; the likelihood is a second one (nmma_em_loglike_lc). */
+int32_t nmma_gp_model_lightcurves(nmma_gp_handle* gp, nmma_em_handle* em, const double* theta_dev, int64_t B, int64_t ld, double* lc_dev,
+                                  void* stream);
+
+/* The remaining outputs of the likelihood-from-curves path for SUPPLIED source-frame curves lc_dev[B][M][NS]: the per-filter pieces
+ * of nmma_em_loglike_parts, and the detector-frame curves of nmma_em_lightcurves (gen_detector_lc's tail, model.py:381-404). */
+int32_t nmma_em_loglike_lc_parts(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld, const double* lc_dev,
+                                 double* chi_dev, double* gp_dev, void* stream);
+int32_t nmma_em_lightcurves_lc(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld, const double* lc_dev,
+                               double* obs_times_dev, double* mag_dev, void* stream);
+
 int32_t nmma_em_profile_begin(nmma_em_handle* h, int32_t max_launches);
 int32_t nmma_em_profile_end(nmma_em_handle* h, double* fused_ms_total, double* combine_ms_total,
                             int32_t* n_launches);

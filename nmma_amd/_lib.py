@@ -19,11 +19,13 @@ SRC_PATH = os.path.join(_HERE, "csrc", "em_kernels.hip")
 #: critical path).  Order = this machine's unit times, longest first (tools: _lib.UNIT_SECONDS after a forced build).
 SOURCES = ("em_kernels.hip", "em_lc64.hip", "em_lc.hip", "em_logl_w3.hip", "em_logl_w2.hip", "em_logl_wc1.hip", "em_logl_w1.hip", "em_logl_f5.hip", "em_logl_f02.hip",
            "em_logl_w4.hip", "em_logl_wc2.hip", "em_logl_w5.hip", "em_logl_f8.hip", "em_logl_f6.hip", "em_logl_f9.hip", "em_logl_f4.hip", "em_logl_f3.hip", "em_logl_f7.hip",
-           "gw_kernels.hip", "em_logl_f1.hip", "walk_kernels.hip")
+           "gw_kernels.hip", "em_logl_f1.hip", "walk_kernels.hip", "em_gp.hip")
 #: per-unit flags after the common ones.  The EM unit keeps -ffp-contract=off (the reference's numpy expressions are not fused and
 #: the parity tests compare bit patterns of intermediate results); the GW unit has no bit-level counterpart (its reference
 #: arithmetic is third-party and absent) and lets hipcc fuse multiply-adds: a quarter fewer instructions in the bin loop.
-UNIT_FLAGS = {"gw_kernels.hip": ["-ffp-contract=fast"]}
+# The GP unit (fp64 only) is kept clear of packed-fp32 instruction selection.
+UNIT_FLAGS = {"gw_kernels.hip": ["-ffp-contract=fast"],
+              "em_gp.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 #: seconds each unit took in this process's last build_library call (tools: order SOURCES longest first)
 UNIT_SECONDS = {}
@@ -89,6 +91,17 @@ class EmConfig(C.Structure):
         ("sys_kind", _pi), ("sys_const", _pd), ("sys_n_nodes", _pi), ("sys_slot_offsets", _pi),
         ("sys_slots", C.POINTER(Slot)), ("sys_node_times", _pd),
         ("stack_operands", C.c_int32), ("n_base_times", C.c_int32), ("base_times", _pd), ("null_filters", _pi),
+    ]
+
+
+class GpConfig(C.Structure):
+    """Mirror of ``struct nmma_gp_config`` (field order must match the header)."""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("device", C.c_int32),
+        ("n_model_filters", C.c_int32), ("n_params", C.c_int32), ("n_coeff", C.c_int32), ("n_tt", C.c_int32),
+        ("n_train", _pi), ("X", _pd), ("alpha", _pd),
+        ("constant", _pd), ("length_scale", _pd), ("rq_alpha", _pd), ("y_mean", _pd), ("y_std", _pd),
+        ("VA", _pd), ("mins", _pd), ("maxs", _pd), ("tt", _pd), ("param_mins", _pd), ("param_maxs", _pd),
     ]
 
 
@@ -203,6 +216,12 @@ PROTOTYPES = {
     "nmma_gw_profile_end": (C.c_int32, [C.c_void_p, _pd, _pi]),
     "nmma_em_coefficients": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                          C.c_void_p]),
+    "nmma_gp_create": (C.c_int32, [C.POINTER(GpConfig), C.POINTER(C.c_void_p)]),
+    "nmma_gp_destroy": (None, [C.c_void_p]),
+    "nmma_gp_coefficients": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nmma_gp_model_lightcurves": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nmma_em_loglike_lc_parts": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nmma_em_lightcurves_lc": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nmma_em_check": (C.c_int32, [C.c_void_p]),
     "nmma_em_debug_timeline": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                            C.POINTER(C.c_int64)]),

@@ -2363,6 +2363,29 @@ int32_t nmma_em_lightcurves(nmma_em_handle* h, const double* theta_dev, int64_t 
     return 0;
 }
 
+int32_t nmma_em_loglike_lc_parts(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld, const double* lc_dev,
+                                 double* chi_dev, double* gp_dev, void* stream) {
+    if (check_call(h, theta_dev, B, ld, "nmma_em_loglike_lc_parts")) return 1;
+    if (B == 0 || h->dev.O == 0) return 0;
+    if (!lc_dev || !chi_dev || !gp_dev) return fail("nmma_em_loglike_lc_parts: null buffer");
+    NM_HIP(hipSetDevice(h->device));
+    if (ensure_scratch(h, B)) return 1;    // the total logL is produced anyway; discard it
+    return launch_lc_loglike(h, theta_dev, B, ld, lc_dev, h->chi, chi_dev, gp_dev, static_cast<hipStream_t>(stream));
+}
+
+int32_t nmma_em_lightcurves_lc(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld, const double* lc_dev,
+                               double* obs_times_dev, double* mag_dev, void* stream) {
+    if (check_call(h, theta_dev, B, ld, "nmma_em_lightcurves_lc")) return 1;
+    if (B == 0) return 0;
+    if (!lc_dev || !obs_times_dev || !mag_dev) return fail("nmma_em_lightcurves_lc: null buffer");
+    if (h->dev.model_kind == NMMA_MODEL_SVD) return fail("nmma_em_lightcurves_lc: an SVD handle evaluates its own curves (nmma_em_lightcurves)");
+    NM_HIP(hipSetDevice(h->device));
+    hipLaunchKernelGGL(lc_to_detector, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream), h->dev_d, theta_dev, (long)B, (long)ld,
+                       lc_dev, obs_times_dev, mag_dev);
+    NM_HIP(hipGetLastError());
+    return 0;
+}
+
 int32_t nmma_em_coefficients(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld, float* coeff_dev,
                              void* stream) {
     if (check_call(h, theta_dev, B, ld, "nmma_em_coefficients")) return 1;

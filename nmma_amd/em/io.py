@@ -19,11 +19,21 @@ import numpy as np
 _KEYS = ("W1", "b1", "W2", "b2", "VA", "mins", "maxs", "tt", "param_mins", "param_maxs")
 
 
+#: a Gaussian-process surrogate (interpolation_type "sklearn_gp") holds these instead of the network's W1, b1, W2, b2:
+#: gp_X [N][NP], gp_alpha [NC][N], gp_const / gp_ell / gp_rq_alpha / gp_ymean / gp_ystd [NC]
+_GP_KEYS = ("gp_X", "gp_alpha", "gp_const", "gp_ell", "gp_rq_alpha", "gp_ymean", "gp_ystd")
+_SVD_KEYS = ("VA", "mins", "maxs", "tt", "param_mins", "param_maxs")
+
+
+def is_gp_model(svd_model):
+    return bool(svd_model) and all("gp_X" in t for t in svd_model.values())
+
+
 def save_svd_model(path, svd_model, model_parameters=None):
     flat = {}
     for filt, t in svd_model.items():
         n_c = int(t["n_coeff"])
-        for k in _KEYS:
+        for k in (_GP_KEYS + _SVD_KEYS if "gp_X" in t else _KEYS):
             a = np.asarray(t[k])
             if k == "VA":
                 a = a[:, :n_c]
@@ -47,10 +57,72 @@ def load_svd_model(path):
     for filt, t in svd.items():
         t["n_coeff"] = int(t["n_coeff"])
         for k in ("W1", "b1", "W2", "b2"):
-            t[k] = np.ascontiguousarray(t[k], dtype=np.float32)
-        for k in ("VA", "mins", "maxs", "tt", "param_mins", "param_maxs"):
-            t[k] = np.ascontiguousarray(t[k], dtype=np.float64)
+            if k in t:
+                t[k] = np.ascontiguousarray(t[k], dtype=np.float32)
+        for k in _SVD_KEYS + _GP_KEYS:
+            if k in t:
+                t[k] = np.ascontiguousarray(t[k], dtype=np.float64)
     return svd, params
+
+
+def extract_gp_arrays(gps, where="GP surrogate"):
+    """The plain arrays of one filter's fitted ``GaussianProcessRegressor`` list (``svd_model[filt]["gps"]``, one per SVD coefficient):
+    ``gp_X [N][NP]`` (``X_train_``, shared by the coefficients), ``gp_alpha [NC][N]`` (``alpha_``) and per coefficient the kernel's
+    constant, length scale and alpha with the target's mean and scale.  Only ``ConstantKernel * RationalQuadratic`` with a scalar length
+    scale is accepted -- what nmma/em/training.py:431-436 builds and the device kernel evaluates; the classes are told by name, so
+    sklearn is needed only to unpickle the objects."""
+    X, alpha, hyper = None, [], {k: [] for k in ("gp_const", "gp_ell", "gp_rq_alpha", "gp_ymean", "gp_ystd")}
+    for i, gp in enumerate(gps):
+        kern = getattr(gp, "kernel_", None)
+        k1, k2 = getattr(kern, "k1", None), getattr(kern, "k2", None)
+        if (type(kern).__name__ != "Product" or type(k1).__name__ != "ConstantKernel" or type(k2).__name__ != "RationalQuadratic"
+                or np.ndim(k2.length_scale) != 0):
+            raise ValueError(f"{where}, coefficient {i}: only ConstantKernel * RationalQuadratic with a scalar length scale is evaluated "
+                             f"on the device (nmma/em/training.py:431-436); found kernel {kern!r}")
+        Xi = np.asarray(gp.X_train_, dtype=np.float64)
+        if X is None:
+            X = Xi
+        elif Xi.shape != X.shape or not np.array_equal(Xi, X):
+            raise ValueError(f"{where}: the coefficients' regressors were fitted on different training sets")
+        a = np.asarray(gp.alpha_, dtype=np.float64)
+        if a.ndim != 1 and not (a.ndim == 2 and a.shape[1] == 1):
+            raise ValueError(f"{where}, coefficient {i}: a regressor with {a.shape[1:]} targets; one per coefficient is expected")
+        alpha.append(a.reshape(-1))
+        hyper["gp_const"].append(float(k1.constant_value))
+        hyper["gp_ell"].append(float(k2.length_scale))
+        hyper["gp_rq_alpha"].append(float(k2.alpha))
+        hyper["gp_ymean"].append(float(np.asarray(gp._y_train_mean).reshape(-1)[0]))
+        hyper["gp_ystd"].append(float(np.asarray(gp._y_train_std).reshape(-1)[0]))
+    if X is None:
+        raise ValueError(f"{where}: no regressors")
+    out = {"gp_X": np.ascontiguousarray(X), "gp_alpha": np.ascontiguousarray(np.stack(alpha))}
+    out.update({k: np.array(v, dtype=np.float64) for k, v in hyper.items()})
+    return out
+
+
+def convert_reference_gp_model(svd_path, model, out_path=None, filters=None):
+    """Read the reference's sklearn_gp layout -- ``{model}.joblib`` plus ``{model}/{filter with ':' -> '_'}.joblib``, each a list of
+    fitted regressors (nmma/em/model.py:623-625, training.py:419-427) -- into the flat arrays, and write the flat ``.npz`` when
+    ``out_path`` is given (a machine without sklearn then loads that)."""
+    import joblib
+    core = "_".join(c for c in model.split("_") if c != "tf")
+    meta = joblib.load(os.path.join(svd_path, f"{core}.joblib"))
+    meta = {k.replace("_", ":"): v for k, v in meta.items()}          # model.py:604-606
+    svd = {}
+    for filt in (filters or list(meta)):
+        if filt not in meta:
+            continue
+        path = os.path.join(svd_path, core, filt.replace(":", "_") + ".joblib")
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"no Gaussian-process file for filter {filt}: {path}")
+        m = meta[filt]
+        t = extract_gp_arrays(joblib.load(path), where=path)
+        t.update({k: np.asarray(m[k], float) for k in _SVD_KEYS})
+        t["n_coeff"] = min(int(m["n_coeff"]), t["gp_alpha"].shape[0])
+        svd[filt] = t
+    if out_path is not None:
+        save_svd_model(out_path, svd)
+    return svd
 
 
 def _h5_datasets(path):

@@ -125,9 +125,12 @@ class SVDLightCurveModel(LightCurveModelContainer):
         self.mag_ncoeff = svd_mag_ncoeff
         self.lbol_ncoeff = svd_lbol_ncoeff
         self.interpolation_type = interpolation_type
-        if interpolation_type not in ("keras", "tensorflow", "torch", "jax"):
-            raise ValueError("nmma_amd evaluates the neural-network surrogates only "
-                             "(--interpolation-type keras/tensorflow); GP surrogates are out of scope")
+        if interpolation_type == "api_gp":
+            raise ValueError("interpolation_type 'api_gp' (GP models served by an external API, nmma/em/model.py:626-631) is out of "
+                             "scope: nmma_amd evaluates the sklearn Gaussian processes ('sklearn_gp') and the neural networks")
+        if interpolation_type not in ("keras", "tensorflow", "torch", "jax", "sklearn_gp"):
+            raise ValueError("nmma_amd evaluates the neural-network surrogates (--interpolation-type keras/tensorflow) and the "
+                             f"sklearn Gaussian processes (sklearn_gp); got {interpolation_type!r}")
         self.svd_path = svd_path
         file_params = None
         if svd_mag_model is None:
@@ -135,6 +138,9 @@ class SVDLightCurveModel(LightCurveModelContainer):
         self.svd_mag_model = {k.replace("_", ":") if "::" not in k and "__" in k else k: v
                               for k, v in svd_mag_model.items()}
         self.svd_lbol_model = None
+        if (interpolation_type == "sklearn_gp") != em_io.is_gp_model(self.svd_mag_model):
+            raise ValueError(f"interpolation_type {interpolation_type!r} does not match the model file: it holds "
+                             + ("Gaussian-process arrays (gp_X, gp_alpha, ...)" if em_io.is_gp_model(self.svd_mag_model) else "no Gaussian-process arrays"))
         if model_parameters is None and file_params is not None and core not in model_parameters_dict:
             model_parameters = file_params
         super().__init__(core, filters, model_parameters, sample_times)
@@ -166,6 +172,8 @@ class SVDLightCurveModel(LightCurveModelContainer):
         if os.path.isfile(flat):
             return em_io.load_svd_model(flat)
         if os.path.isfile(os.path.join(svd_path, f"{core}.joblib")):
+            if interpolation_type == "sklearn_gp":
+                return em_io.convert_reference_gp_model(svd_path, core, flat, filters), None
             itype = "tensorflow" if os.path.isdir(os.path.join(svd_path, f"{core}_tf")) else interpolation_type
             return em_io.convert_reference_model(svd_path, core, flat, filters, itype), None
         raise ValueError(f"Model file not found under {svd_path}")
@@ -188,6 +196,8 @@ class SVDLightCurveModel(LightCurveModelContainer):
                   sample_times=None if self._default_times() else self.model_times,
                   cosmo_grid=self.cosmo_grid, ebv_coeff=self.ebv_coeff, device=self.device,
                   n_coeff=self.mag_ncoeff, hubble_reference=getattr(self, "hubble_reference", None))
+        if self.interpolation_type == "sklearn_gp":
+            kw["model_kind"] = "svd_gp"
         # extinction (get_extinction_mags, model.py:323-342): caller-supplied linear coefficients win; else the
         # default host-frame SMC law is evaluated natively when the filter frequencies are known
         if self.ebv_coeff is None and self.extinction_law == "P92_SMC_host" and self.filter_nu0 is not None:
@@ -600,8 +610,8 @@ class CombinedLightCurveModelContainer(_TensorModelMixin):
         if len(self.lc_models) != 2:
             return None
         for i, m in enumerate(self.lc_models):
-            if not isinstance(m, SVDLightCurveModel):
-                continue
+            if not isinstance(m, SVDLightCurveModel) or m.interpolation_type == "sklearn_gp":
+                continue        # (a Gaussian-process surrogate has no one-launch form: its curves are materialised)
             # (the filters the model LISTS: one without a surrogate is its null output -- +inf on every node, "radio and X-ray filters
             #  when using with GRB data", lightcurve_generation.py:168-169 -- and rides along as a null filter of the engine)
             if list(m.filters) == self.filters and len(m.gpu_filters) > 0:

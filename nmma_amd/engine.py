@@ -117,10 +117,18 @@ class EMEngine:
         self.observed_filters = list(observed_filters)
         self.device = int(device)
 
-        kinds = {"svd": L.MODEL_SVD, "me2017": L.MODEL_ME2017, "external": L.MODEL_EXTERNAL}
+        # "svd_gp": the SVD model with the Gaussian-process surrogate -- an external-kind handle (theta layout, sample_times, the
+        # likelihood from curves) next to an nmma_gp_handle that evaluates the curves (one launch each)
+        kinds = {"svd": L.MODEL_SVD, "me2017": L.MODEL_ME2017, "external": L.MODEL_EXTERNAL, "svd_gp": L.MODEL_EXTERNAL}
         if model_kind not in kinds:
             raise L.NMMAHipError(f"unknown model_kind {model_kind!r}")
         self.model_kind = model_kind
+        self._gp = None
+        gp_cfg = None
+        if model_kind == "svd_gp":
+            gp_cfg, gp_keep, n_c, n_t = self._gp_config(svd_model, model_filters, model_parameters, n_coeff)
+            if sample_times is None:
+                sample_times = np.asarray(svd_model[model_filters[0]]["tt"], dtype=np.float64)
         cfg = L.EmConfig()
         keep = []
         cfg.abi_version, cfg.device = L.ABI_VERSION, self.device
@@ -174,7 +182,10 @@ class EMEngine:
         else:
             if sample_times is None:
                 raise L.NMMAHipError("sample_times are required for non-SVD models")
-            n_p, n_h, n_c, n_t = len(model_parameters), 0, 0, 0
+            n_p = len(model_parameters)
+            n_h = 0
+            if gp_cfg is None:
+                n_c = n_t = 0
             tt = None
             cfg.n_params = n_p
         if filter_nu0 is not None:
@@ -320,6 +331,51 @@ class EMEngine:
         self.n_sample_times = int(lib.nmma_em_n_sample_times(h))
         self.flops_per_eval = int(lib.nmma_em_flops_per_eval(h))
         del keep
+        if gp_cfg is not None:
+            gp_cfg.abi_version, gp_cfg.device = L.ABI_VERSION, self.device
+            g = C.c_void_p()
+            L.check(lib.nmma_gp_create(C.byref(gp_cfg), C.byref(g)), "nmma_gp_create")
+            self._gp = g
+            del gp_keep
+
+    @staticmethod
+    def _gp_config(svd_model, model_filters, model_parameters, n_coeff):
+        """``nmma_gp_config`` of a Gaussian-process surrogate: per filter ``gp_X [N][NP]``, ``gp_alpha [NC][N]`` and the hyperparameter
+        rows (``nmma_amd.em.io.extract_gp_arrays``); the training sets may differ between filters.  ``n_coeff`` below the trained count
+        truncates (lightcurve_generation.py:182-185)."""
+        first = svd_model[model_filters[0]]
+        if "gp_X" not in first:
+            raise L.NMMAHipError("model_kind 'svd_gp' needs the Gaussian-process arrays (gp_X, gp_alpha, ...) of every filter")
+        nc_trained = min(int(svd_model[f]["n_coeff"]) for f in model_filters)
+        n_c = min(int(n_coeff), nc_trained) if n_coeff else nc_trained
+        n_p, n_t = int(np.asarray(first["gp_X"]).shape[1]), len(first["tt"])
+        if len(model_parameters) != n_p:
+            raise L.NMMAHipError("model_parameters do not match the surrogate input width")
+        if not 1 <= n_c <= L.MAX_COEFF:
+            raise L.NMMAHipError(f"n_coeff must be 1 .. {L.MAX_COEFF}")
+        for f in model_filters:
+            t = svd_model[f]
+            X, a = np.asarray(t["gp_X"]), np.asarray(t["gp_alpha"])
+            if X.ndim != 2 or X.shape[1] != n_p or a.ndim != 2 or a.shape[1] != X.shape[0] or a.shape[0] < n_c or len(t["tt"]) != n_t:
+                raise L.NMMAHipError(f"filter {f}: Gaussian-process array shapes are inconsistent")
+        cat = lambda k, cut: _f64(np.concatenate([np.asarray(svd_model[f][k], dtype=np.float64)[cut].reshape(-1) for f in model_filters]))
+        arrays = dict(
+            n_train=_i32([np.asarray(svd_model[f]["gp_X"]).shape[0] for f in model_filters]),
+            X=cat("gp_X", slice(None)), alpha=cat("gp_alpha", slice(0, n_c)),
+            constant=cat("gp_const", slice(0, n_c)), length_scale=cat("gp_ell", slice(0, n_c)), rq_alpha=cat("gp_rq_alpha", slice(0, n_c)),
+            y_mean=cat("gp_ymean", slice(0, n_c)), y_std=cat("gp_ystd", slice(0, n_c)),
+            VA=cat("VA", (slice(None), slice(0, n_c))), mins=cat("mins", slice(None)), maxs=cat("maxs", slice(None)), tt=cat("tt", slice(None)),
+            param_mins=cat("param_mins", slice(None)), param_maxs=cat("param_maxs", slice(None)))
+        cfg = L.GpConfig()
+        cfg.n_model_filters, cfg.n_params, cfg.n_coeff, cfg.n_tt = len(model_filters), n_p, n_c, n_t
+        for k, a in arrays.items():
+            setattr(cfg, k, _ptr(a, C.c_int32 if k == "n_train" else C.c_double))
+        return cfg, arrays, n_c, n_t
+
+    def _refuse_gp(self, what):
+        if self._gp is not None:
+            raise L.NMMAHipError(f"{what}: not served by a Gaussian-process engine (model_kind 'svd_gp' evaluates the surrogate and the likelihood "
+                                 "in two launches: loglike, loglike_parts, lightcurves, model_lightcurves, coefficients)")
 
     @staticmethod
     def _systematics_arrays(spec, obs, names, fixed):
@@ -410,6 +466,17 @@ class EMEngine:
         """logL for every row of ``theta[B, D]``.  torch CUDA tensor in -> torch tensor out
         (asynchronous on ``stream``, default torch's current stream); numpy in -> numpy out (synchronous)."""
         import torch
+        if self._gp is not None:
+            t = self._dev_theta(theta)
+            if out is None:
+                out = torch.empty(t.shape[0], dtype=torch.float64, device=t.device)
+            else:
+                self._check_out(out, t.shape[0])
+            lc = self._gp_curves(t, stream)
+            L.check(self._lib.nmma_em_loglike_lc(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
+                                                 C.c_void_p(lc.data_ptr()), C.c_void_p(out.data_ptr()), self._stream(stream)),
+                    "nmma_em_loglike_lc")
+            return out if isinstance(theta, torch.Tensor) else out.cpu().numpy()
         if not isinstance(theta, torch.Tensor):
             th = _f64(theta)
             if th.ndim != 2 or th.shape[1] < len(self.parameter_names):
@@ -433,6 +500,16 @@ class EMEngine:
                                           C.c_void_p(out.data_ptr()), self._stream(stream)), "nmma_em_loglike")
         return out
 
+    def _gp_curves(self, t, stream=None):
+        """Source-frame curves lc[B, M, NS] of a Gaussian-process engine for the device rows ``t`` (``nmma_gp_model_lightcurves``)."""
+        import torch
+        lc = torch.empty((t.shape[0], len(self.model_filters), self.n_sample_times), dtype=torch.float64, device=t.device)
+        if stream is not None:
+            lc.record_stream(stream)
+        L.check(self._lib.nmma_gp_model_lightcurves(self._gp, self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
+                                                    C.c_void_p(lc.data_ptr()), self._stream(stream)), "nmma_gp_model_lightcurves")
+        return lc
+
     def loglike_parts(self, theta):
         """(chi[O, B], gp[O, B]) per observed filter (em_likelihood.py:337-352)."""
         import torch
@@ -440,6 +517,12 @@ class EMEngine:
         n_o = self._n_obs_uploaded            # (incl. the bands without data that stand for unobserved model filters)
         chi = torch.empty((n_o, t.shape[0]), dtype=torch.float64, device=t.device)
         gp = torch.empty_like(chi)
+        if self._gp is not None:
+            lc = self._gp_curves(t)
+            L.check(self._lib.nmma_em_loglike_lc_parts(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0), C.c_void_p(lc.data_ptr()),
+                                                       C.c_void_p(chi.data_ptr()), C.c_void_p(gp.data_ptr()), self._stream()),
+                    "nmma_em_loglike_lc_parts")
+            return chi, gp
         L.check(self._lib.nmma_em_loglike_parts(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
                                                 C.c_void_p(chi.data_ptr()), C.c_void_p(gp.data_ptr()),
                                                 self._stream()), "nmma_em_loglike_parts")
@@ -453,6 +536,12 @@ class EMEngine:
         ns, m = self.n_sample_times, len(self.model_filters)
         tobs = torch.empty((t.shape[0], ns), dtype=torch.float64, device=t.device)
         mag = torch.empty((t.shape[0], m, ns), dtype=torch.float64, device=t.device)
+        if self._gp is not None:
+            lc = self._gp_curves(t)
+            L.check(self._lib.nmma_em_lightcurves_lc(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0), C.c_void_p(lc.data_ptr()),
+                                                     C.c_void_p(tobs.data_ptr()), C.c_void_p(mag.data_ptr()), self._stream()),
+                    "nmma_em_lightcurves_lc")
+            return tobs, mag
         L.check(self._lib.nmma_em_lightcurves(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
                                               C.c_void_p(tobs.data_ptr()), C.c_void_p(mag.data_ptr()),
                                               self._stream()), "nmma_em_lightcurves")
@@ -462,6 +551,8 @@ class EMEngine:
         """Source-frame absolute magnitudes lc[B, M, NS] of the handle's model (generate_lightcurve)."""
         import torch
         t = self._dev_theta(theta)
+        if self._gp is not None:
+            return self._gp_curves(t)
         lc = torch.empty((t.shape[0], len(self.model_filters), self.n_sample_times), dtype=torch.float64,
                          device=t.device)
         L.check(self._lib.nmma_em_model_lightcurves(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
@@ -515,6 +606,7 @@ class EMEngine:
         ``completed=True``: ``lc2`` came out of ``regrid`` (its non-finite nodes are leading / trailing only: no flux wherever they lie).
         After a None, ``stack2_reason`` says why the handle has no one-launch form."""
         import torch
+        self._refuse_gp("loglike_stack2")
         t = self._dev_theta(theta)
         shape = (t.shape[0], len(self.model_filters), self.n_sample_times)
         lc2 = lc2.to(device=t.device, dtype=torch.float64).contiguous()
@@ -573,9 +665,15 @@ class EMEngine:
         return out
 
     def coefficients(self, theta):
-        """SVD coefficients c[B, M, NC] (fp32), the surrogate output (lightcurve_generation.py:198)."""
+        """SVD coefficients c[B, M, NC], the surrogate output: fp32 from the network (lightcurve_generation.py:198), fp64 from a
+        Gaussian-process engine (:206-211)."""
         import torch
         t = self._dev_theta(theta)
+        if self._gp is not None:
+            c = torch.empty((t.shape[0], len(self.model_filters), self.n_coeff), dtype=torch.float64, device=t.device)
+            L.check(self._lib.nmma_gp_coefficients(self._gp, self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
+                                                   C.c_void_p(c.data_ptr()), self._stream()), "nmma_gp_coefficients")
+            return c
         c = torch.empty((t.shape[0], len(self.model_filters), self.n_coeff), dtype=torch.float32, device=t.device)
         L.check(self._lib.nmma_em_coefficients(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
                                                C.c_void_p(c.data_ptr()), self._stream()), "nmma_em_coefficients")
@@ -631,6 +729,7 @@ class EMEngine:
         device, packed ``u | v | logl | counts`` per row (``nmma_walk_queue::records_dev``; :func:`nmma_amd.parallel.unpack_records` reads them), instead
         of being downloaded: the send buffer of a queue sharded over ranks (``parallel.ShardedQueue``); ``walk_queue_end`` returns None."""
         import torch
+        self._refuse_gp("walk_queue")
         live, u0 = _f64(live), _f64(u0)
         n, ndim = u0.shape
         if len(table) != ndim or live.ndim != 2 or live.shape[1] != ndim or ndim != len(self.parameter_names):
@@ -681,6 +780,9 @@ class EMEngine:
         if getattr(self, "_walk_ws", None):
             self._lib.nmma_walk_ws_destroy(self._walk_ws)
             self._walk_ws = None
+        if getattr(self, "_gp", None):
+            self._lib.nmma_gp_destroy(self._gp)
+            self._gp = None
         if getattr(self, "_handle", None):
             self._lib.nmma_em_destroy(self._handle)
             self._handle = None
