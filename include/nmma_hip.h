@@ -67,8 +67,12 @@ enum nmma_model_kind {
     NMMA_MODEL_SVD = 0,       /* SVDLightCurveModel: surrogate tensors required (model.py:535-731)   */
     NMMA_MODEL_ME2017 = 1,    /* SimpleKilonovaLightCurveModel("Me2017"): analytic, needs filter_nu0
                                  (model.py:1280-1337, lightcurve_generation.py:566-652)              */
-    NMMA_MODEL_EXTERNAL = 2   /* light curves supplied per call (nmma_em_loglike_lc): GRB afterglow,
+    NMMA_MODEL_EXTERNAL = 2,  /* light curves supplied per call (nmma_em_loglike_lc): GRB afterglow,
                                  combined models (model.py:1342-1510)                               */
+    NMMA_MODEL_PIRO2021 = 3   /* ShockCoolingLightCurveModel("Piro2021"): closed form, needs filter_nu0, the 3 parameters
+                                 log10_Menv, log10_Renv, log10_Ee and sample times > 0
+                                 (model.py:1230-1277, lightcurve_generation.py:314-363); served by every entry
+                                 point that serves NMMA_MODEL_ME2017                                  */
 };
 
 enum nmma_sys_kind {
@@ -87,7 +91,7 @@ typedef struct nmma_em_config {
 
     int32_t model_kind;           /* enum nmma_model_kind; the surrogate tensors below are used by
                                      NMMA_MODEL_SVD only (pass NULL / 0 otherwise, with n_tt = 0)    */
-    const double* filter_nu0;     /* [M] observer-frame filter frequencies in Hz (NMMA_MODEL_ME2017;
+    const double* filter_nu0;     /* [M] observer-frame filter frequencies in Hz (NMMA_MODEL_ME2017, NMMA_MODEL_PIRO2021;
                                      c / lambda, model.py:226) or NULL                              */
 
     /* ---- SVD surrogate: eval_svd_model, nmma/em/lightcurve_generation.py:180-217 ---- */
@@ -556,7 +560,9 @@ int32_t nmma_em_coefficients(nmma_em_handle* h, const double* theta_dev, int64_t
 /* Run-time options of a handle, for A/B measurements and tests (each also has an environment variable that is read once, at
  * nmma_em_create): "walk_fuse" (NMMA_WALK_NO_FUSE), "walk_split" (NMMA_WALK_NO_SPLIT): 0 / 1; "lc_group" (NMMA_LC_GROUP): 0 = by batch
  * size, 16 / 32 / 64 lanes per sample of the likelihood-from-curves kernel; "stack2_fixup" (NMMA_STACK2_NO_FIXUP): 0 skips the
- * re-evaluation launches of nmma_em_loglike_stack2 (measurement only).  Unknown names fail. */
+ * re-evaluation launches of nmma_em_loglike_stack2 (measurement only); "sc_tile": rows per workgroup of the Piro2021 kernel (0 = 8,
+ * fewer where the grid needs the room; 1 .. 64 to measure); "sc_probe": 1 / 2 = that kernel's magnitude phase without its stores /
+ * without its transcendentals (measurement only: the curves are then NOT the model's).  Unknown names fail. */
 int32_t nmma_em_set_option(nmma_em_handle* h, const char* name, int32_t value);
 
 /* Introspection used by bench.py / tests. */

@@ -181,7 +181,7 @@ int32_t nmma_em_create(const nmma_em_config* c, nmma_em_handle** out) {
     std::vector<unsigned char> ltab_host;
     bool fold = false;
     int fold_bytes = 0, fold_off_b2 = 0, unfold_tab_bytes = 0, unfold_off_b2 = 0;
-    if (c->model_kind < NMMA_MODEL_SVD || c->model_kind > NMMA_MODEL_EXTERNAL) return fail("nmma_em_create: bad model_kind");
+    if (c->model_kind < NMMA_MODEL_SVD || c->model_kind > NMMA_MODEL_PIRO2021) return fail("nmma_em_create: bad model_kind");
     if (M < 1 || NP < 0 || NP > NMMA_MAX_PARAMS) return fail("nmma_em_create: bad model dimensions");
     if (svd && (NP < 1 || NH < 1 || NC < 1 || NC > NMMA_MAX_COEFF || NT < 2))
         return fail("nmma_em_create: bad surrogate dimensions");
@@ -209,6 +209,12 @@ int32_t nmma_em_create(const nmma_em_config* c, nmma_em_handle** out) {
                     "outside a combination such a band floors every sample");
     if (c->model_kind == NMMA_MODEL_ME2017 && (!c->filter_nu0 || NP != 4))
         return fail("nmma_em_create: Me2017 needs filter_nu0 and its 4 parameters (log10_mej, log10_vej, beta, log10_kappa_r)");
+    if (c->model_kind == NMMA_MODEL_PIRO2021) {
+        if (!c->filter_nu0 || NP != 3)
+            return fail("nmma_em_create: Piro2021 needs filter_nu0 and its 3 parameters (log10_Menv, log10_Renv, log10_Ee)");
+        for (int j = 0; j < c->n_sample_times; ++j)       // (the model divides by t: sc_bol_lc, lightcurve_generation.py:333-346)
+            if (!(c->sample_times[j] > 0.0)) return fail("nmma_em_create: Piro2021 needs every sample time > 0");
+    }
     if (c->redshift_mode == NMMA_Z_GRID && (c->n_cosmo < 2 || !c->dist_grid || !c->z_grid))
         return fail("nmma_em_create: redshift grid missing");
     auto slot_ok = [&](const nmma_slot& s) { return s.col < D && s.op >= 0 && s.op <= NMMA_OP_ACOS; };
@@ -1496,6 +1502,8 @@ int32_t nmma_em_set_option(nmma_em_handle* h, const char* name, int32_t value) {
     else if (n == "walk_split") h->walk_split = value != 0;
     else if (n == "lc_group") { if (value != 0 && value != 16 && value != 32 && value != 64) return fail("nmma_em_set_option: lc_group is 0, 16, 32 or 64"); h->lc_group = value; }
     else if (n == "stack2_fixup") h->stack2_fixup = value != 0;
+    else if (n == "sc_tile") { if (value < 0 || value > 64) return fail("nmma_em_set_option: sc_tile is 0 .. 64"); h->sc_tile = value; }
+    else if (n == "sc_probe") { if (value < 0 || value > 2) return fail("nmma_em_set_option: sc_probe is 0, 1 or 2"); h->sc_probe = value; }
     else return fail("nmma_em_set_option: unknown option '" + n + "'");
     return 0;
 }
@@ -1672,6 +1680,7 @@ static int launch_model_lc(nmma_em_handle* h, const double* theta, int64_t B, in
         NM_HIP(hipGetLastError());
         return 0;
     }
+    if (P.model_kind == NMMA_MODEL_PIRO2021) return launch_piro2021_lc(h, theta, B, ld, lc, s);
     return fail("this handle's model has no light-curve kernel (NMMA_MODEL_EXTERNAL: supply the curves)");
 }
 

@@ -48,7 +48,9 @@ struct nmma_em_handle {
     int walk_lanes = 0;             // "walk_lanes" : 0 = 8 lanes per chain up to 8 sampled dimensions, 16 beyond; 16 = always 16 (measurement)
     int walk_split = 1;             // "walk_split" / NMMA_WALK_NO_SPLIT: small queues' fused launches split by band
     int lc_group = 0;               // "lc_group"   / NMMA_LC_GROUP, NMMA_LC_NO_GROUPS: lanes per sample of em_lc_loglike (0: by batch size; 16 / 32 / 64)
-    int stack2_fixup = 1;           // "stack2_fixup" / NMMA_STACK2_NO_FIXUP: re-evaluation launches of nmma_em_loglike_stack2 (0: measurement only)
+    int sc_tile = 0;                // "sc_tile"    : rows per workgroup of piro2021_lc (0: 8, fewer where the node arrays need the room; measurement: 1 .. 64)
+    int sc_probe = 0;               // "sc_probe"   : piro2021_lc's measurement forms (1: phase C without its stores, 2: without its transcendentals; 0: the kernel)
+    int stack2_fixup = 1;          // "stack2_fixup" / NMMA_STACK2_NO_FIXUP: re-evaluation launches of nmma_em_loglike_stack2 (0: measurement only)
     int walk_tab_mask = 0;          // fused-MCMC-step forms (bit 2 (R - 1) + (16 lanes per chain)) that give way to two launches: the log Phi table of the upper limits would cost them a ring slot
     int stack2_ok = 0;              // the handle has the one-launch form of the combined model (em_logl<.., 7>; nmma_em_loglike_stack2)
     std::string stack2_why;         // ... or why not (what nmma_last_error says after status 2)
@@ -140,5 +142,8 @@ template <int R, int KP, int NMW, int NVW, int FAST, int WALKF = 0>
 hipError_t launch_logl_one(nmma_em_handle* h, const double* theta, int64_t B, int64_t ld, double* out,
                            double* chi, double* gp, hipStream_t s, const nmma_walk_fuse* wf = nullptr, uint64_t wstep = 0, int wlast = 0,
                            EmAux aux = EmAux{nullptr, nullptr, nullptr});
+
+// piro2021_lc's launcher (em_sc.hip): source-frame absolute magnitudes lc[B][M][NS] of an NMMA_MODEL_PIRO2021 handle; 0 or fail()'s 1
+int launch_piro2021_lc(nmma_em_handle* h, const double* theta, int64_t B, int64_t ld, double* lc, hipStream_t s);
 
 }  // namespace nmma

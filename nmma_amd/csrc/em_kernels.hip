@@ -338,9 +338,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void s
 // explicit-Euler time loop is sequential, the per-step layer sum and the photosphere
 // argmin are wave reductions.  Output: source-frame absolute magnitudes lc[B][M][NS].
 // =======================================================================================
-namespace me17 {
-constexpr double msun = 1.988409870698051e33, c_cgs = 2.99792458e10, h_cgs = 6.62607015e-27, kb = 1.380649e-16;
-constexpr double sigSB = 5.6703744191844314e-05, D10pc = 10 * 3.085677581491367e18, day = 86400.0;
+namespace me17 {      // (the cgs constants: em_math.h)
 constexpr int MPREC = 300, NL = MPREC - 1, LPL = 5;   // layers per lane (5 * 64 >= 299)
 }  // namespace me17
 

@@ -35,6 +35,12 @@ constexpr double kNormPdfLogC = 0.9189385332046727;  // log(sqrt(2*pi)) (scipy _
 NM_HD double dinf() { return HUGE_VAL; }
 NM_HD double dnan() { return HUGE_VAL - HUGE_VAL; }
 
+// cgs constants of the analytic blackbody models (nmma/core/constants.py with astropy's CODATA-2018 values): me2017_lc, piro2021_lc
+namespace me17 {
+constexpr double msun = 1.988409870698051e33, c_cgs = 2.99792458e10, h_cgs = 6.62607015e-27, kb = 1.380649e-16;
+constexpr double sigSB = 5.6703744191844314e-05, D10pc = 10 * 3.085677581491367e18, day = 86400.0;
+}  // namespace me17
+
 // ---------------------------------------------------------------------------
 // theta column -> physical scalar (nmma/core/conversion.py:119-126, em/model.py:272-286)
 // ---------------------------------------------------------------------------

@@ -299,14 +299,16 @@ def _is_number(v):
 HOST_ONLY_MODELS = ("TrPi2018", "Piro2021", "PL_BB_fixedT", "Sr2023", "Arnett")
 
 
-def create_light_curve_model_from_args(em_transient, args, filters=None, sample_times=None, host_models=None):
+def create_light_curve_model_from_args(em_transient, args, filters=None, sample_times=None, host_models=None, device_models=()):
     """Factory with the reference's shape (model.py:1617-1668, :1591-1614): ``em_transient`` is a model name or a comma-separated
     list / list of names; EVERY sub-model gets the same ``filters`` and ``sample_times = setup_sample_times(args)`` (which is what
     makes a two-model combination eligible for the one-launch likelihood); more than one name gives a
     :class:`CombinedLightCurveModelContainer`.  Names: ``Me2017`` -> the analytic kilonova on the device; a key of ``host_models``
     -> an :class:`ExternalLightCurveModel` around that object's ``generate_lightcurve`` (a model whose arithmetic is third-party
     code and stays on the host: the reference's ``GRBLightCurveModel`` for ``TrPi2018``, its supernova / shock-cooling / host-galaxy
-    models); anything else is an SVD surrogate, as in the reference's own fall-through (model.py:1585-1587)."""
+    models); a name in ``device_models`` that the device can build (``DEVICE_MODEL_CLASSES``: ``Piro2021`` -> the shock-cooling
+    model's own kernel) needs no host object; anything else is an SVD surrogate, as in the reference's own fall-through
+    (model.py:1585-1587)."""
     from . import utils
     names = em_transient.split(",") if isinstance(em_transient, str) else list(em_transient)
     names = [n.strip() for n in names]
@@ -318,14 +320,19 @@ def create_light_curve_model_from_args(em_transient, args, filters=None, sample_
     # names the reference maps to models whose arithmetic is third-party or not built here (model.py:1572-1586: afterglowpy, the
     # shock-cooling / host-galaxy / bolometric / power-law black-body models): they need the host object -- falling through to the SVD
     # surrogate would fail later with an unrelated missing-file error
-    missing = [n for n in names if n in HOST_ONLY_MODELS and n not in host_models]
+    unknown = [n for n in device_models if n not in DEVICE_MODEL_CLASSES]
+    if unknown:
+        raise ValueError(f"device_models {unknown}: the device builds {sorted(DEVICE_MODEL_CLASSES)} only")
+    missing = [n for n in names if n in HOST_ONLY_MODELS and n not in host_models and n not in device_models]
     if missing:
         raise ValueError(f"model(s) {missing} are evaluated on the host: pass host_models={{name: model}} -- an object with the reference's "
                          "generate_lightcurve(sample_times, parameters) and model_parameters -- the likelihood then takes their curves as an operand")
     law = getattr(args, "em_extinction_law", None)
     models = []
     for name in names:
-        if name in host_models:
+        if name in device_models and name not in host_models:
+            m = DEVICE_MODEL_CLASSES[name](name, filters=filters, sample_times=sample_times)
+        elif name in host_models:
             host = host_models[name]
             if sample_times is None:
                 raise ValueError(f"host model {name!r}: sample_times are needed (--em-tmin / --em-tmax)")
@@ -423,6 +430,49 @@ class SimpleKilonovaLightCurveModel(_TensorModelMixin, LightCurveModelContainer)
         scalar = all(np.ndim(parameters[k]) == 0 for k in names)
         lc = {f: (mag[0, i] if scalar else mag[:, i]) for i, f in enumerate(self.filters)}
         return (tobs[0] if scalar else tobs), lc
+
+
+class ShockCoolingLightCurveModel(_TensorModelMixin, LightCurveModelContainer):
+    """The Piro2021 shock-cooling model on the GPU (reference: model.py:1230-1277; ``sc_bol_lc`` / ``sc_lc``,
+    lightcurve_generation.py:314-363).  Closed form per node: kernel ``piro2021_lc`` balances (row, node) and (row, filter, node)
+    items over its workgroups.  The bolometric form (``filters=None``) is not built."""
+
+    gpu_model_kind = "piro2021"
+
+    def __init__(self, model="Piro2021", filters=None, model_parameters=None, sample_times=None, filter_lambdas=None,
+                 cosmo_grid=None, device=0):
+        if model != "Piro2021":
+            raise ValueError("nmma_amd implements the Piro2021 shock-cooling model only")
+        if filters is None:
+            raise ValueError("ShockCoolingLightCurveModel: the bolometric form (filters=None, sc_bol_lc alone) is not evaluated on the "
+                             "device: pass the filters of the photometry")
+        if model_parameters is None:
+            model_parameters = ["log10_Menv", "log10_Renv", "log10_Ee"]
+        super().__init__(model, filters, model_parameters, sample_times)
+        if len(self.model_parameters) != 3:
+            raise ValueError("Piro2021 takes three parameters, in the order log10_Menv, log10_Renv, log10_Ee")
+        if not np.all(np.asarray(self.model_times) > 0):
+            raise ValueError("Piro2021 divides by the time since the explosion: every sample time must be > 0")
+        lam = dict(BUILTIN_FILTER_LAMBDAS)
+        lam.update(filter_lambdas or {})
+        missing = [f for f in self.filters if f not in lam]
+        if missing:
+            raise ValueError(f"effective wavelengths needed for filters {missing} (pass filter_lambdas)")
+        self.lambdas = np.array([lam[f] for f in self.filters])
+        self.nu_0s = C_SI / self.lambdas
+        self.filter_nu0 = dict(zip(self.filters, self.nu_0s))
+        self.cosmo_grid, self.device = cosmo_grid, device
+        self._lc_engine, self._lc_names = None, None
+
+    def setup_model_times(self):
+        """model.py:1257-1260: hours to a few days."""
+        return np.geomspace(1.0 / 24.0, 3.5, 100)
+
+    gen_detector_lc = SimpleKilonovaLightCurveModel.gen_detector_lc
+
+
+#: names of ``HOST_ONLY_MODELS`` the device can build when the caller asks for them (``device_models=`` of the factory)
+DEVICE_MODEL_CLASSES = {"Piro2021": ShockCoolingLightCurveModel}
 
 
 class ExternalLightCurveModel(_TensorModelMixin, LightCurveModelContainer):

@@ -119,7 +119,9 @@ class EMEngine:
 
         # "svd_gp": the SVD model with the Gaussian-process surrogate -- an external-kind handle (theta layout, sample_times, the
         # likelihood from curves) next to an nmma_gp_handle that evaluates the curves (one launch each)
-        kinds = {"svd": L.MODEL_SVD, "me2017": L.MODEL_ME2017, "external": L.MODEL_EXTERNAL, "svd_gp": L.MODEL_EXTERNAL}
+        # "piro2021": the shock-cooling model, closed form per node (kernel piro2021_lc), served like "me2017"
+        kinds = {"svd": L.MODEL_SVD, "me2017": L.MODEL_ME2017, "external": L.MODEL_EXTERNAL, "svd_gp": L.MODEL_EXTERNAL,
+                 "piro2021": L.MODEL_PIRO2021}
         if model_kind not in kinds:
             raise L.NMMAHipError(f"unknown model_kind {model_kind!r}")
         self.model_kind = model_kind
@@ -707,7 +709,7 @@ class EMEngine:
 
     def set_option(self, name, value):
         """Run-time option of the handle (``nmma_em_set_option``): "walk_fuse", "walk_split" (0 / 1), "lc_group" (0, 16, 32, 64),
-        "stack2_fixup" (0 / 1) -- for A/B measurements and tests."""
+        "stack2_fixup" (0 / 1), "sc_tile" (0 .. 64), "sc_probe" (0, 1, 2) -- for A/B measurements and tests."""
         L.check(self._lib.nmma_em_set_option(self._handle, str(name).encode(), int(value)), "nmma_em_set_option")
 
     def check(self):
