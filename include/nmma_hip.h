@@ -633,6 +633,53 @@ int32_t nmma_em_loglike_lc_parts(nmma_em_handle* h, const double* theta_dev, int
 int32_t nmma_em_lightcurves_lc(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld, const double* lc_dev,
                                double* obs_times_dev, double* mag_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Bolometric light curves: SimpleBolometricLightCurveModel ("Arnett" / "Arnett_modified", nmma/em/model.py:494-532,
+ * lightcurve_generation.py:65-138) and BasicEMTransient's likelihood of a bolometric luminosity curve (em_likelihood.py:136-263).
+ * One kernel (bol_logl, csrc/em_bol.hip) takes theta to log L; the curves stay on the chip unless asked for.  With x = t / tau_m,
+ * y = tau_m / (2 tau_ni), s = tau_m (tau_co - tau_ni) / (2 tau_co tau_ni) and S(q) = exp(-x^2) int_0^x 2 z exp(z^2 - 2 q z) dz:
+ *     Lbol = Mni ((eps_ni - eps_co) S(y) + eps_co S(y - s)),  Mni = 10^log10_mni msun;  Arnett_modified: times 1 - exp(-(t_0 / t)^2)
+ * detector frame: times t (1 + z) + timeshift, Lbol / (1 + z)^2.  The likelihood interpolates the finite nodes linearly, extrapolates
+ * through the first / last two (utils.autocomplete_data, extrapolate = "linear"), and sums the terms of nmma_em_loglike with an
+ * infinite detection limit: a detection where sqrt(unc^2 + err^2) is finite, an upper limit otherwise. */
+enum nmma_bol_model { NMMA_BOL_SUPPLIED = 0, NMMA_BOL_ARNETT = 1, NMMA_BOL_ARNETT_MODIFIED = 2 };
+
+typedef struct nmma_bol_config {
+    int32_t abi_version, device;
+    int32_t model_kind;                 /* enum nmma_bol_model; NMMA_BOL_SUPPLIED serves nmma_bol_loglike_lc only */
+    int32_t n_sample_times;             /* NS >= 2 */
+    const double* sample_times;         /* [NS] source-frame days, strictly ascending, >= 0 (> 0 for Arnett_modified) */
+    int32_t n_data;                     /* N >= 1 */
+    const double* data_times;           /* [N] days since the trigger */
+    const double* data_values;          /* [N] luminosities */
+    const double* data_sigmas;          /* [N] their uncertainties; +inf: an upper limit */
+    int32_t n_dim;                      /* columns of theta a slot may name */
+    nmma_slot tau_m, log10_mni, t_0;    /* t_0: Arnett_modified only */
+    nmma_slot timeshift, redshift, luminosity_distance;
+    nmma_slot em_syserr;                /* the constant error budget, or the sampled column */
+    int32_t redshift_mode;              /* NMMA_Z_SLOT: `redshift`; NMMA_Z_GRID: np.interp(luminosity_distance; dist_grid, z_grid); NMMA_Z_ZERO */
+    int32_t n_cosmo;
+    const double* dist_grid;            /* [n_cosmo] */
+    const double* z_grid;               /* [n_cosmo] */
+} nmma_bol_config;
+
+typedef struct nmma_bol_handle nmma_bol_handle;
+/* Validates (grids that do not fit the kernel's LDS are refused here) and uploads. */
+int32_t nmma_bol_create(const nmma_bol_config* cfg, nmma_bol_handle** out);
+void nmma_bol_destroy(nmma_bol_handle* h);
+/* logl_dev[B] from theta_dev[B][ld]; NMMA_LOGL_FLOOR for a NaN sum or a curve with fewer than two finite nodes.  Asynchronous on `stream`. */
+int32_t nmma_bol_loglike(nmma_bol_handle* h, const double* theta_dev, int64_t B, int64_t ld, double* logl_dev, void* stream);
+/* gen_detector_lc: obs_times_dev[B][NS] = t (1 + z) + timeshift and lbol_dev[B][NS] = Lbol / (1 + z)^2 */
+int32_t nmma_bol_lightcurves(nmma_bol_handle* h, const double* theta_dev, int64_t B, int64_t ld, double* obs_times_dev, double* lbol_dev,
+                             void* stream);
+/* generate_lightcurve: the source-frame curve lbol_dev[B][NS] */
+int32_t nmma_bol_model_lightcurves(nmma_bol_handle* h, const double* theta_dev, int64_t B, int64_t ld, double* lbol_dev, void* stream);
+/* log L of SUPPLIED source-frame curves lbol_dev[B][NS] (any model kind): theta supplies redshift, timeshift and em_syserr */
+int32_t nmma_bol_loglike_lc(nmma_bol_handle* h, const double* theta_dev, int64_t B, int64_t ld, const double* lbol_dev, double* logl_dev,
+                            void* stream);
+/* "probe": 1 = nmma_bol_loglike without the likelihood phase (measurement: the share of the curve generator); 0 = the kernel */
+int32_t nmma_bol_set_option(nmma_bol_handle* h, const char* name, int32_t value);
+
 int32_t nmma_em_profile_begin(nmma_em_handle* h, int32_t max_launches);
 int32_t nmma_em_profile_end(nmma_em_handle* h, double* fused_ms_total, double* combine_ms_total,
                             int32_t* n_launches);

@@ -19,13 +19,13 @@ SRC_PATH = os.path.join(_HERE, "csrc", "em_kernels.hip")
 #: critical path).  Order = this machine's unit times, longest first (tools: _lib.UNIT_SECONDS after a forced build).
 SOURCES = ("em_kernels.hip", "em_lc64.hip", "em_lc.hip", "em_logl_w3.hip", "em_logl_w2.hip", "em_logl_wc1.hip", "em_logl_w1.hip", "em_logl_f5.hip", "em_logl_f02.hip",
            "em_logl_w4.hip", "em_logl_wc2.hip", "em_logl_w5.hip", "em_logl_f8.hip", "em_logl_f6.hip", "em_logl_f9.hip", "em_logl_f4.hip", "em_logl_f3.hip", "em_logl_f7.hip",
-           "gw_kernels.hip", "em_logl_f1.hip", "walk_kernels.hip", "em_gp.hip", "em_sc.hip")
+           "gw_kernels.hip", "em_logl_f1.hip", "walk_kernels.hip", "em_gp.hip", "em_sc.hip", "em_bol.hip")
 #: per-unit flags after the common ones.  The EM unit keeps -ffp-contract=off (the reference's numpy expressions are not fused and
 #: the parity tests compare bit patterns of intermediate results); the GW unit has no bit-level counterpart (its reference
 #: arithmetic is third-party and absent) and lets hipcc fuse multiply-adds: a quarter fewer instructions in the bin loop.
-# The GP and shock-cooling units (fp64 only) are kept clear of packed-fp32 instruction selection.
+# The GP, shock-cooling and bolometric units (fp64 only) are kept clear of packed-fp32 instruction selection.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-UNIT_FLAGS = {"gw_kernels.hip": ["-ffp-contract=fast"], "em_gp.hip": _NO_PACKED_FP32, "em_sc.hip": _NO_PACKED_FP32}
+UNIT_FLAGS = {"gw_kernels.hip": ["-ffp-contract=fast"], "em_gp.hip": _NO_PACKED_FP32, "em_sc.hip": _NO_PACKED_FP32, "em_bol.hip": _NO_PACKED_FP32}
 
 #: seconds each unit took in this process's last build_library call (tools: order SOURCES longest first)
 UNIT_SECONDS = {}
@@ -45,6 +45,7 @@ Z_ZERO, Z_SLOT, Z_GRID = range(3)
 SYS_CONST, SYS_PARAM, SYS_NODES = range(3)
 MODEL_SVD, MODEL_ME2017, MODEL_EXTERNAL, MODEL_PIRO2021 = range(4)
 EXT_LINEAR, EXT_P92_SMC_HOST = range(2)
+BOL_SUPPLIED, BOL_ARNETT, BOL_ARNETT_MODIFIED = range(3)
 
 
 class NMMAHipError(RuntimeError):
@@ -102,6 +103,19 @@ class GpConfig(C.Structure):
         ("n_train", _pi), ("X", _pd), ("alpha", _pd),
         ("constant", _pd), ("length_scale", _pd), ("rq_alpha", _pd), ("y_mean", _pd), ("y_std", _pd),
         ("VA", _pd), ("mins", _pd), ("maxs", _pd), ("tt", _pd), ("param_mins", _pd), ("param_maxs", _pd),
+    ]
+
+
+class BolConfig(C.Structure):
+    """Mirror of ``struct nmma_bol_config`` (field order must match the header)."""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("device", C.c_int32), ("model_kind", C.c_int32),
+        ("n_sample_times", C.c_int32), ("sample_times", _pd),
+        ("n_data", C.c_int32), ("data_times", _pd), ("data_values", _pd), ("data_sigmas", _pd),
+        ("n_dim", C.c_int32),
+        ("tau_m", Slot), ("log10_mni", Slot), ("t_0", Slot), ("timeshift", Slot), ("redshift", Slot), ("luminosity_distance", Slot),
+        ("em_syserr", Slot),
+        ("redshift_mode", C.c_int32), ("n_cosmo", C.c_int32), ("dist_grid", _pd), ("z_grid", _pd),
     ]
 
 
@@ -220,6 +234,13 @@ PROTOTYPES = {
     "nmma_gp_destroy": (None, [C.c_void_p]),
     "nmma_gp_coefficients": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nmma_gp_model_lightcurves": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nmma_bol_create": (C.c_int32, [C.POINTER(BolConfig), C.POINTER(C.c_void_p)]),
+    "nmma_bol_destroy": (None, [C.c_void_p]),
+    "nmma_bol_loglike": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nmma_bol_lightcurves": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nmma_bol_model_lightcurves": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nmma_bol_loglike_lc": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nmma_bol_set_option": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_int32]),
     "nmma_em_loglike_lc_parts": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nmma_em_lightcurves_lc": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nmma_em_check": (C.c_int32, [C.c_void_p]),

@@ -1,5 +1,5 @@
 """EM likelihood plugin (``nmma/em/em_likelihood.py``): ``EMTransientLikelihood``
-wrapping ``MultiFilterTransient`` -- same constructors, attributes and per-sample
+wrapping ``MultiFilterTransient`` (photometry per filter) or ``BasicEMTransient`` (a bolometric luminosity curve) -- same constructors, attributes and per-sample
 ``log_likelihood(parameters)`` as the reference, plus the batched entry point
 ``log_likelihood_batch(theta)`` that evaluates a whole live-point set in one launch.
 
@@ -12,6 +12,76 @@ import numpy as np
 from ..core.base import LOGL_FLOOR, NMMALikelihood, fixed_value, is_constraint
 from ..core.conversion import convert_mtot_mni
 from . import utils
+
+
+class BasicEMTransient:
+    """A bolometric EM transient (em_likelihood.py:136-263) on the GPU: the model's curve, ``autocomplete_data`` at the data epochs and
+    the Gaussian / survival-function terms are one launch of kernel ``bol_logl`` (:class:`nmma_amd.engine.BolometricEngine`)."""
+
+    def __init__(self, light_curve_model, light_curve_data, systematics_handler, priors, detection_limit, verbose):
+        self.light_curve_model = light_curve_model
+        self.light_curve_model.check_vs_priors(priors)
+        (self.light_curve_times, self.light_curves,
+         self.light_curve_uncertainties, self.trigger_time) = light_curve_data
+        if getattr(systematics_handler, "table", None) is not None or hasattr(systematics_handler, "filters"):
+            raise ValueError("a bolometric light curve takes the plain SystematicsHandler (a constant error budget or one sampled "
+                             "em_syserr): filter-wise and time-node systematics are not evaluated for it")
+        systematics_handler.reset(self.light_curve_model.model_times, priors)
+        self.systematics_handler = systematics_handler
+        self.verbose = verbose
+        self.priors = priors
+        self._engine, self._names = None, None
+        self.set_detection_limit(detection_limit)
+
+    def set_detection_limit(self, detection_limit):
+        if not (np.ndim(detection_limit) == 0 and detection_limit == np.inf):
+            raise ValueError("a finite detection_limit is not evaluated for bolometric light curves (a truncation in luminosity; "
+                             "the reference's bolometric_setup never passes one)")
+        self.detection_limit = detection_limit
+
+    def __repr__(self):
+        return f"{self.__class__.__name__} (light_curve_model={self.light_curve_model})"
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_engine"] = None          # rebuilt lazily per process
+        return state
+
+    def sampling_layout(self):
+        return MultiFilterTransient.sampling_layout(self)
+
+    def engine(self, names=None):
+        from ..engine import BolometricEngine
+        names = list(names if names is not None else (self._names or self.sampling_layout()[0]))
+        MultiFilterTransient._check_names(names)
+        if self._engine is None or names != self._names:
+            if self._engine is not None:
+                self._engine.close()
+            _, fixed = self.sampling_layout()
+            model, handler = self.light_curve_model, self.systematics_handler
+            if handler.sampled and handler.base_prior_name != "em_syserr":
+                raise ValueError("the bolometric kernel reads the sampled systematic error from the column 'em_syserr'")
+            self._engine = BolometricEngine(model.model, names, model.model_times, fixed={k: v for k, v in fixed.items() if k not in names},
+                                            data=(self.light_curve_times, self.light_curves, self.light_curve_uncertainties),
+                                            cosmo_grid=model.cosmo_grid, error_budget=handler.error_budget_value,
+                                            device=getattr(model, "device", 0))
+            self._names = names
+        return self._engine
+
+    def log_likelihood(self, parameters):
+        """One parameter dict -> float (em_likelihood.py:186-204); -inf where the reference returns its floor."""
+        names = self._names or [n for n in self.sampling_layout()[0] if n in parameters]
+        val = float(self.engine(names).loglike(np.array([[float(parameters[n]) for n in names]]))[0])
+        if self.verbose:
+            print(parameters, val)
+        return -np.inf if val == LOGL_FLOOR else val
+
+    def log_likelihood_batch(self, theta, names=None, external_lc=None):
+        """theta[B, D] (numpy or torch CUDA tensor; columns = ``names`` or the sampled prior keys) -> logL[B], floor applied."""
+        return self.engine(names).loglike(theta)
+
+    def final_diagnostics(self, bestfit_params, args, result=None):
+        return self.light_curve_model.gen_detector_lc(dict(bestfit_params))
 
 
 class MultiFilterTransient:
@@ -197,6 +267,11 @@ class EMTransientLikelihood(NMMALikelihood):
 
     def __init__(self, light_curve_model, light_curve_data, systematics_handler, priors, filters=None,
                  detection_limit=np.inf, verbose=False, **kwargs):
+        if not filters and not isinstance(light_curve_data[0], dict):
+            # no filters and a plain array of epochs: a bolometric light curve (em_likelihood.py:84-87)
+            sub_model = BasicEMTransient(light_curve_model, light_curve_data, systematics_handler, priors, detection_limit, verbose)
+            super().__init__(sub_model, priors, **kwargs)
+            return
         if not filters:
             filters = list(light_curve_data[0].keys())
         sub_model = MultiFilterTransient(filters, light_curve_model, light_curve_data, systematics_handler,
@@ -274,6 +349,21 @@ def build_em_likelihood(light_curve_model, light_curve_data, trigger_time, prior
     handler = FilterSystematicsHandler(filters, systematics_file, error_budget, data[0])
     return EMTransientLikelihood(light_curve_model, data, handler, priors, filters=filters,
                                  detection_limit=detection_limit, verbose=verbose)
+
+
+def build_bolometric_likelihood(light_curve_data, trigger_time, priors, em_model="Arnett", sample_times=None, systematics_file=None,
+                                error_budget=None, cosmo_grid=None, verbose=False, device=0):
+    """A bolometric table -> ready likelihood, in the order of the reference's ``bolometric_setup`` (em/analysis.py:72-108): the
+    epochs relative to the trigger and sorted, the Arnett model on ``sample_times`` (None: the model's own grid), the plain
+    systematics handler on the epochs, then the likelihood.
+
+    ``light_curve_data``: columns ``phase``, ``Lbb``, ``Lbb_unc`` (structured array, dict of arrays or data frame)."""
+    from .model import SimpleBolometricLightCurveModel
+    from .systematics import SystematicsHandler
+    data = utils.setup_bolometric_lc_data(light_curve_data, trigger_time)
+    model = SimpleBolometricLightCurveModel(em_model, sample_times=sample_times, cosmo_grid=cosmo_grid, device=device)
+    handler = SystematicsHandler(systematics_file, error_budget, data[0])
+    return EMTransientLikelihood(model, data, handler, priors, verbose=verbose)
 
 
 #: legacy (<= 0.2.x) name used by BASELINE.json's north_star

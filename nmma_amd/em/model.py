@@ -471,6 +471,64 @@ class ShockCoolingLightCurveModel(_TensorModelMixin, LightCurveModelContainer):
     gen_detector_lc = SimpleKilonovaLightCurveModel.gen_detector_lc
 
 
+class SimpleBolometricLightCurveModel(LightCurveModelContainer):
+    """Arnett's bolometric supernova light curves on the GPU (reference: model.py:494-532; ``arnett_lc`` / ``arnett_modified_lc``,
+    lightcurve_generation.py:65-138).  The curve generator is phase A of kernel ``bol_logl``
+    (:class:`nmma_amd.engine.BolometricEngine`); the reference's factory does not build this model, and neither does
+    ``create_light_curve_model_from_args``: construct it directly (``build_bolometric_likelihood``)."""
+
+    def __init__(self, model="Arnett", sample_times=None, cosmo_grid=None, device=0, **em_model_kwargs):
+        if model not in ("Arnett", "Arnett_modified"):
+            raise ValueError("SimpleBolometricLightCurveModel: model is 'Arnett' or 'Arnett_modified'")
+        mp = ["tau_m", "log10_mni"] + (["t_0"] if model == "Arnett_modified" else [])
+        super().__init__(model, None, mp, sample_times)
+        st = np.asarray(self.model_times, float)
+        if st.ndim != 1 or len(st) < 2 or not np.all(np.diff(st) > 0):
+            raise ValueError(f"{model}: sample_times must be at least two strictly ascending times")
+        if st[0] < 0 or (model == "Arnett_modified" and st[0] <= 0):
+            raise ValueError(f"{model}: sample times must be " + ("> 0 (the modified form divides by the time since the explosion)"
+                                                                  if model == "Arnett_modified" else ">= 0"))
+        self.cosmo_grid, self.device = cosmo_grid, device
+        self._lc_engine, self._lc_names = None, None
+
+    def setup_model_times(self):
+        """model.py:518-523."""
+        return np.linspace(0.005, 20.0, 40)
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_lc_engine"], state["_lc_names"] = None, None
+        return state
+
+    def _curves(self, parameters, sample_times, detector):
+        from ..engine import BolometricEngine
+        if sample_times is not None and not np.array_equal(sample_times, self.model_times):
+            self.model_times, self._lc_engine = np.asarray(sample_times, float), None
+        names = sorted(k for k, v in parameters.items() if np.ndim(v) <= 1 and _is_number(v))
+        if self._lc_engine is None or names != self._lc_names:
+            if self._lc_engine is not None:
+                self._lc_engine.close()
+            self._lc_engine = BolometricEngine(self.model, names, self.model_times, cosmo_grid=self.cosmo_grid, device=self.device)
+            self._lc_names = names
+        cols = [np.atleast_1d(np.asarray(parameters[k], float)) for k in names]
+        n = max(len(c) for c in cols)
+        theta = np.stack([np.broadcast_to(c, (n,)) for c in cols], axis=1)
+        scalar = all(np.ndim(parameters[k]) == 0 for k in names)
+        if not detector:
+            lbol = self._lc_engine.model_lightcurves(theta)
+            return lbol[0] if scalar else lbol
+        tobs, lbol = self._lc_engine.lightcurves(theta)
+        return (tobs[0], lbol[0]) if scalar else (tobs, lbol)
+
+    def generate_lightcurve(self, sample_times, parameters):
+        """Source-frame ``lbol[NS]`` (``[B, NS]`` for equal-length arrays) -- model.py:530-532."""
+        return self._curves(parameters, sample_times, detector=False)
+
+    def gen_detector_lc(self, parameters=None, sample_times=None):
+        """``(obs_times, lbol)`` in the detector frame: ``t (1 + z) + timeshift`` and ``lbol / (1 + z)^2`` (model.py:352-376, :525-528)."""
+        return self._curves(_with_host_redshift(parameters, self.cosmo_grid), sample_times, detector=True)
+
+
 #: names of ``HOST_ONLY_MODELS`` the device can build when the caller asks for them (``device_models=`` of the factory)
 DEVICE_MODEL_CLASSES = {"Piro2021": ShockCoolingLightCurveModel}
 

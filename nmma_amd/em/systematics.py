@@ -144,6 +144,43 @@ def apply_rules(rules, filters, priors):
     return table
 
 
+class SystematicsHandler:
+    """The reference's plain handler (:14-192) for a light curve without filters (``BasicEMTransient``): a constant error budget, or
+    one sampled scalar ``em_syserr``.  Time-node systematics are refused: the bolometric kernel has no per-node table."""
+
+    def __init__(self, systematics_file=None, error_budget=None, light_curve_times=np.linspace(0.1, 14, 10), base_prior_name="em_syserr"):
+        self.base_prior_name = base_prior_name
+        self.light_curve_times = np.asarray(light_curve_times, float)
+        self.adjust_error_budget(error_budget)
+        if isinstance(systematics_file, str):
+            systematics_file = load_yaml(systematics_file)
+        self.systematics_dict = systematics_file if isinstance(systematics_file, dict) else {}
+        if "config" in self.systematics_dict:
+            raise ValueError("the legacy 'config:' systematics document addresses filters: a bolometric light curve has none")
+        if node_grid(self.systematics_dict, (0.0, 1.0)) is not None:
+            raise ValueError("time-node systematics (time_nodes / time_range) are not evaluated for bolometric light curves: "
+                             "give one sampled em_syserr prior or a constant error budget")
+        self.sampled = False
+
+    def adjust_error_budget(self, error_budget):
+        """Reference :44-49 (its default here is 0.0001, not the filter handler's 1)."""
+        budget = 0.0001 if error_budget is None else float(error_budget)
+        self.error_budget_value = budget
+        self.error_budget = np.full_like(self.light_curve_times, budget)
+
+    def reset(self, model_times, priors):
+        """Reference :187-192: a document, or a prior named ``base_prior_name``, means the sampled scalar."""
+        self.time_range = (model_times[0], model_times[-1])
+        if self.systematics_dict and self.base_prior_name not in priors:
+            raise AssertionError("Required systematics prior missing")
+        self.sampled = bool(self.systematics_dict) or self.base_prior_name in priors
+
+    def __call__(self, parameters):
+        if self.sampled:
+            return np.full_like(self.light_curve_times, parameters[self.base_prior_name])
+        return self.error_budget
+
+
 class FilterSystematicsHandler:
     """Same constructor, ``reset`` and per-sample call as the reference's handler (:163-210)."""
 

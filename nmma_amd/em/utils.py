@@ -71,6 +71,14 @@ def setup_filtered_lc_data(light_curve_data, trigger_time):
     return (lc_times, lc_mags, lc_unc, trigger_time)
 
 
+def setup_bolometric_lc_data(light_curve_data, trigger_time):
+    """utils.py:352-360: a table with the columns ``phase``, ``Lbb`` and ``Lbb_unc`` (a structured array, a dict of arrays or a
+    data frame) -> (times since the trigger, luminosities, uncertainties, trigger_time), sorted by phase."""
+    phase, lbb, unc = (np.asarray(light_curve_data[k], float) for k in ("phase", "Lbb", "Lbb_unc"))
+    order = np.argsort(phase)
+    return (phase[order] - trigger_time, lbb[order], unc[order], trigger_time)
+
+
 def cut_data_to_time_range(data, args=None, trigger_time=0.0, tmin=0, tmax=np.inf):
     """utils.py:233-253: keep the rows of every filter whose time since the trigger lies in [data_tmin, data_tmax]
     (taken from ``args`` when it has them), dropping filters left empty.  ``data``: ``{filt: {time, mag, mag_error}}`` in MJD."""

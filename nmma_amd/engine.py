@@ -794,3 +794,117 @@ class EMEngine:
             self.close()
         except Exception:
             pass
+
+
+class BolometricEngine:
+    """Owns one ``nmma_bol_handle``: the Arnett bolometric models and the likelihood of a bolometric luminosity curve (kernel
+    ``bol_logl``: one launch from ``theta`` to log L).
+
+    Parameters
+    ----------
+    model : "Arnett", "Arnett_modified", or None (curves are supplied: ``loglike_lc`` only)
+    parameter_names : list[str]   columns of ``theta``
+    fixed : dict  fixed parameters (``tau_m, log10_mni, t_0, timeshift, redshift, luminosity_distance, em_syserr``)
+    sample_times : array [NS]  source-frame days
+    data : (times, values, uncertainties) arrays, or None (a curves-only engine)
+    cosmo_grid : (dist_grid, z_grid) or None; used when no ``redshift`` is sampled or fixed and a ``luminosity_distance`` is
+    error_budget : the constant systematic error, used unless ``em_syserr`` is sampled or fixed
+    """
+
+    KINDS = {None: L.BOL_SUPPLIED, "Arnett": L.BOL_ARNETT, "Arnett_modified": L.BOL_ARNETT_MODIFIED}
+
+    def __init__(self, model, parameter_names, sample_times, fixed=None, data=None, cosmo_grid=None, error_budget=1e-4, device=0):
+        self._handle = None
+        self._lib = lib = L.load_library()
+        if model not in self.KINDS:
+            raise L.NMMAHipError(f"unknown bolometric model {model!r} (Arnett, Arnett_modified, or None for supplied curves)")
+        names, fixed = list(parameter_names), dict(fixed or {})
+        self.parameter_names, self.model, self.device = names, model, int(device)
+        st = _f64(sample_times)
+        self.n_sample_times = len(st)
+        # (a curves-only engine: one upper limit that is never evaluated by the curve entry points)
+        dt, dv, ds = (_f64(a) for a in (data if data is not None else ([0.0], [0.0], [np.inf])))
+        if not (dt.ndim == dv.ndim == ds.ndim == 1 and len(dt) == len(dv) == len(ds)):
+            raise L.NMMAHipError("bolometric data: times, values and uncertainties must be 1-D arrays of one length")
+        cfg = L.BolConfig()
+        cfg.abi_version, cfg.device, cfg.model_kind = L.ABI_VERSION, self.device, self.KINDS[model]
+        cfg.n_sample_times, cfg.sample_times = len(st), _ptr(st, C.c_double)
+        cfg.n_data = len(dt)
+        cfg.data_times, cfg.data_values, cfg.data_sigmas = (_ptr(a, C.c_double) for a in (dt, dv, ds))
+        cfg.n_dim = len(names)
+
+        def slot(key, default=None):
+            if key not in names and key not in fixed and default is None:
+                raise KeyError(f"bolometric model parameter {key!r} is neither sampled nor fixed (sampled: {names}, fixed: {sorted(fixed)})")
+            return _plain_slot(key, names, fixed, default)
+
+        generated = model is not None
+        cfg.tau_m = slot("tau_m") if generated else L.Slot.constant(1.0)
+        cfg.log10_mni = slot("log10_mni") if generated else L.Slot.constant(0.0)
+        cfg.t_0 = slot("t_0") if model == "Arnett_modified" else L.Slot.constant(0.0)
+        cfg.timeshift = slot("timeshift", 0.0)
+        cfg.em_syserr = slot("em_syserr", float(error_budget))
+        cfg.redshift, cfg.luminosity_distance = L.Slot.constant(0.0), L.Slot.constant(_AVG_DEFAULT_LD)
+        keep = [st, dt, dv, ds]
+        if "redshift" in names or "redshift" in fixed:
+            cfg.redshift_mode, cfg.redshift = L.Z_SLOT, slot("redshift")
+        elif ("luminosity_distance" in names or "luminosity_distance" in fixed) and cosmo_grid is not None:
+            dg, zg = _f64(cosmo_grid[0]), _f64(cosmo_grid[1])
+            keep += [dg, zg]
+            cfg.redshift_mode, cfg.luminosity_distance = L.Z_GRID, slot("luminosity_distance")
+            cfg.n_cosmo, cfg.dist_grid, cfg.z_grid = len(dg), _ptr(dg, C.c_double), _ptr(zg, C.c_double)
+        else:
+            cfg.redshift_mode = L.Z_ZERO         # neither: the reference's get_redshift answers 0 (conversion.py:62-64)
+        handle = C.c_void_p()
+        L.check(lib.nmma_bol_create(C.byref(cfg), C.byref(handle)), "nmma_bol_create")
+        self._handle = handle
+
+    _dev_theta = EMEngine._dev_theta
+    _stream = EMEngine._stream
+
+    def _call(self, fn, theta, shapes, extra=()):
+        import torch
+        t = self._dev_theta(theta)
+        outs = [torch.empty((t.shape[0],) + s, dtype=torch.float64, device=t.device) for s in shapes]
+        args = [C.c_void_p(e.data_ptr()) for e in extra] + [C.c_void_p(o.data_ptr()) for o in outs]
+        L.check(getattr(self._lib, fn)(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0), *args, self._stream()), fn)
+        if not isinstance(theta, torch.Tensor):
+            outs = [o.cpu().numpy() for o in outs]
+        return outs[0] if len(outs) == 1 else tuple(outs)
+
+    def loglike(self, theta):
+        """log L for every row of ``theta[B, D]``: torch CUDA tensor in -> tensor out (asynchronous), numpy in -> numpy out."""
+        return self._call("nmma_bol_loglike", theta, [()])
+
+    def lightcurves(self, theta):
+        """(obs_times[B, NS], lbol[B, NS]) in the detector frame -- ``gen_detector_lc`` for every row."""
+        return self._call("nmma_bol_lightcurves", theta, [(self.n_sample_times,)] * 2)
+
+    def model_lightcurves(self, theta):
+        """Source-frame lbol[B, NS] -- ``generate_lightcurve`` for every row."""
+        return self._call("nmma_bol_model_lightcurves", theta, [(self.n_sample_times,)])
+
+    def loglike_lc(self, theta, lbol):
+        """log L from supplied source-frame curves ``lbol[B, NS]``."""
+        import torch
+        t = self._dev_theta(theta)
+        lc = (lbol if isinstance(lbol, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(lbol, dtype=np.float64)))
+        lc = lc.to(device=t.device, dtype=torch.float64).contiguous()
+        if tuple(lc.shape) != (t.shape[0], self.n_sample_times):
+            raise L.NMMAHipError(f"lbol must be [B, NS] = {(t.shape[0], self.n_sample_times)}, got {tuple(lc.shape)}")
+        out = self._call("nmma_bol_loglike_lc", t, [()], extra=(lc,))
+        return out if isinstance(theta, torch.Tensor) else out.cpu().numpy()
+
+    def set_option(self, name, value):
+        L.check(self._lib.nmma_bol_set_option(self._handle, name.encode(), int(value)), "nmma_bol_set_option")
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._lib.nmma_bol_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
