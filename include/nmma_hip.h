@@ -69,10 +69,15 @@ enum nmma_model_kind {
                                  (model.py:1280-1337, lightcurve_generation.py:566-652)              */
     NMMA_MODEL_EXTERNAL = 2,  /* light curves supplied per call (nmma_em_loglike_lc): GRB afterglow,
                                  combined models (model.py:1342-1510)                               */
-    NMMA_MODEL_PIRO2021 = 3   /* ShockCoolingLightCurveModel("Piro2021"): closed form, needs filter_nu0, the 3 parameters
+    NMMA_MODEL_PIRO2021 = 3,  /* ShockCoolingLightCurveModel("Piro2021"): closed form, needs filter_nu0, the 3 parameters
                                  log10_Menv, log10_Renv, log10_Ee and sample times > 0
                                  (model.py:1230-1277, lightcurve_generation.py:314-363); served by every entry
                                  point that serves NMMA_MODEL_ME2017                                  */
+    NMMA_MODEL_HONA2020 = 4   /* SimpleKilonovaLightCurveModel("HoNa2020"): the Hotokezaka & Nakar semi-analytic kilonova, 99 shells
+                                 integrated by scipy's adaptive RK45 (kernel hona2020_lc); needs filter_nu0, the 6 parameters
+                                 log10_mej, vej_max, vej_min, vej_frac, log10_kappa_low_vej, log10_kappa_high_vej (model.py:59-66)
+                                 and strictly ascending sample times >= 0.05 d spanning more than 0.05 d
+                                 (lightcurve_generation.py:654-771); served by every entry point that serves NMMA_MODEL_ME2017 */
 };
 
 enum nmma_sys_kind {
@@ -91,7 +96,7 @@ typedef struct nmma_em_config {
 
     int32_t model_kind;           /* enum nmma_model_kind; the surrogate tensors below are used by
                                      NMMA_MODEL_SVD only (pass NULL / 0 otherwise, with n_tt = 0)    */
-    const double* filter_nu0;     /* [M] observer-frame filter frequencies in Hz (NMMA_MODEL_ME2017, NMMA_MODEL_PIRO2021;
+    const double* filter_nu0;     /* [M] observer-frame filter frequencies in Hz (NMMA_MODEL_ME2017, _PIRO2021, _HONA2020;
                                      c / lambda, model.py:226) or NULL                              */
 
     /* ---- SVD surrogate: eval_svd_model, nmma/em/lightcurve_generation.py:180-217 ---- */
@@ -226,6 +231,11 @@ int32_t nmma_em_lightcurves(nmma_em_handle* h, const double* theta_dev, int64_t 
  * (generate_lightcurve: model.py:707-728 for SVD, :1321-1337 for Me2017). */
 int32_t nmma_em_model_lightcurves(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld,
                                   double* lc_dev, void* stream);
+
+/* Diagnostic of an NMMA_MODEL_HONA2020 handle: steps_dev[B][2] int32 = (accepted, rejected) steps of the adaptive integration of
+ * every row (what scipy's solve_ivp takes for the same row: len(out.t) - 1 and the rejected attempts); a row that hit one of the
+ * kernel's caps reports the counts it reached.  Runs the light-curve kernel into the handle's workspace.  Asynchronous. */
+int32_t nmma_em_hona_steps(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld, int32_t* steps_dev, void* stream);
 
 /* Likelihood from SUPPLIED source-frame light curves lc_dev[B][M][NS] on the handle's
  * sample_times (+inf / NaN where a model has no value): the tail of the reference path from

@@ -181,7 +181,7 @@ int32_t nmma_em_create(const nmma_em_config* c, nmma_em_handle** out) {
     std::vector<unsigned char> ltab_host;
     bool fold = false;
     int fold_bytes = 0, fold_off_b2 = 0, unfold_tab_bytes = 0, unfold_off_b2 = 0;
-    if (c->model_kind < NMMA_MODEL_SVD || c->model_kind > NMMA_MODEL_PIRO2021) return fail("nmma_em_create: bad model_kind");
+    if (c->model_kind < NMMA_MODEL_SVD || c->model_kind > NMMA_MODEL_HONA2020) return fail("nmma_em_create: bad model_kind");
     if (M < 1 || NP < 0 || NP > NMMA_MAX_PARAMS) return fail("nmma_em_create: bad model dimensions");
     if (svd && (NP < 1 || NH < 1 || NC < 1 || NC > NMMA_MAX_COEFF || NT < 2))
         return fail("nmma_em_create: bad surrogate dimensions");
@@ -214,6 +214,19 @@ int32_t nmma_em_create(const nmma_em_config* c, nmma_em_handle** out) {
             return fail("nmma_em_create: Piro2021 needs filter_nu0 and its 3 parameters (log10_Menv, log10_Renv, log10_Ee)");
         for (int j = 0; j < c->n_sample_times; ++j)       // (the model divides by t: sc_bol_lc, lightcurve_generation.py:333-346)
             if (!(c->sample_times[j] > 0.0)) return fail("nmma_em_create: Piro2021 needs every sample time > 0");
+    }
+    if (c->model_kind == NMMA_MODEL_HONA2020) {
+        if (!c->filter_nu0 || NP != 6)
+            return fail("nmma_em_create: HoNa2020 needs filter_nu0 and its 6 parameters (log10_mej, vej_max, vej_min, vej_frac, "
+                        "log10_kappa_low_vej, log10_kappa_high_vej)");
+        // what the reference or scipy would refuse: the integration runs from the first node to the last with a first step of 0.05 d
+        // (solve_ivp: "first_step exceeds bounds"), the spline's and np.interp's abscissae ascend, the model starts at 0.05 d
+        const int n = c->n_sample_times;
+        for (int j = 0; j < n; ++j)
+            if (!(c->sample_times[j] >= 0.05) || (j > 0 && !(c->sample_times[j] > c->sample_times[j - 1])))
+                return fail("nmma_em_create: HoNa2020 needs strictly ascending sample times, none below 0.05 d");
+        if (!(c->sample_times[n - 1] * 86400.0 - c->sample_times[0] * 86400.0 > 0.05 * 86400.0))
+            return fail("nmma_em_create: HoNa2020 needs sample times that span more than the integrator's first step of 0.05 d");
     }
     if (c->redshift_mode == NMMA_Z_GRID && (c->n_cosmo < 2 || !c->dist_grid || !c->z_grid))
         return fail("nmma_em_create: redshift grid missing");
@@ -1681,6 +1694,7 @@ static int launch_model_lc(nmma_em_handle* h, const double* theta, int64_t B, in
         return 0;
     }
     if (P.model_kind == NMMA_MODEL_PIRO2021) return launch_piro2021_lc(h, theta, B, ld, lc, s);
+    if (P.model_kind == NMMA_MODEL_HONA2020) return launch_hona2020_lc(h, theta, B, ld, lc, nullptr, s);
     return fail("this handle's model has no light-curve kernel (NMMA_MODEL_EXTERNAL: supply the curves)");
 }
 
@@ -1695,6 +1709,16 @@ int32_t nmma_em_model_lightcurves(nmma_em_handle* h, const double* theta_dev, in
         return 0;
     }
     return launch_model_lc(h, theta_dev, B, ld, lc_dev, static_cast<hipStream_t>(stream));
+}
+
+int32_t nmma_em_hona_steps(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld, int32_t* steps_dev, void* stream) {
+    if (check_call(h, theta_dev, B, ld, "nmma_em_hona_steps")) return 1;
+    if (h->dev.model_kind != NMMA_MODEL_HONA2020) return fail("nmma_em_hona_steps: not a HoNa2020 handle");
+    if (B == 0) return 0;
+    if (!steps_dev) return fail("nmma_em_hona_steps: null output");
+    NM_HIP(hipSetDevice(h->device));
+    if (ensure_lc_ws(h, B)) return 1;
+    return launch_hona2020_lc(h, theta_dev, B, ld, h->lc_ws, steps_dev, static_cast<hipStream_t>(stream));
 }
 
 int32_t nmma_em_loglike_lc(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld, const double* lc_dev,

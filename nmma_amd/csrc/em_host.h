@@ -146,4 +146,8 @@ hipError_t launch_logl_one(nmma_em_handle* h, const double* theta, int64_t B, in
 // piro2021_lc's launcher (em_sc.hip): source-frame absolute magnitudes lc[B][M][NS] of an NMMA_MODEL_PIRO2021 handle; 0 or fail()'s 1
 int launch_piro2021_lc(nmma_em_handle* h, const double* theta, int64_t B, int64_t ld, double* lc, hipStream_t s);
 
+// hona2020_lc's launcher (em_kn.hip): the same contract for an NMMA_MODEL_HONA2020 handle; steps (or nullptr): int32 [B][2] accepted /
+// rejected steps of every row's integration
+int launch_hona2020_lc(nmma_em_handle* h, const double* theta, int64_t B, int64_t ld, double* lc, int32_t* steps, hipStream_t s);
+
 }  // namespace nmma

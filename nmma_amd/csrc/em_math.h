@@ -41,6 +41,20 @@ constexpr double msun = 1.988409870698051e33, c_cgs = 2.99792458e10, h_cgs = 6.6
 constexpr double sigSB = 5.6703744191844314e-05, D10pc = 10 * 3.085677581491367e18, day = 86400.0;
 }  // namespace me17
 
+// The blackbody magnitude of one (filter, node) of those models (lightcurve_generation.py:43-58, utils.py:793-811): piro2021_lc, hona2020_lc.
+//   x = min(h nu (1 / T) / kb, 700)     (np.clip(., None, 700); NaN passes through)
+//   F = 2 h / c^2 nu^3 / expm1(x) R R / D^2 with nu^3 = (nu nu) nu;  mag = F > 0 ? -2.5 log10 F - 48.6 : +inf
+NM_HD double bb_exponent(double nu, double inv_T) {
+    double ex = me17::h_cgs * nu * inv_T / me17::kb;
+    if (ex > 700) ex = 700;
+    return ex;
+}
+NM_HD double bb_abs_mag(double nu, double inv_T, double R, double& F) {
+    using namespace me17;
+    F = 2.0 * h_cgs / (c_cgs * c_cgs) * (nu * nu * nu) / expm1(bb_exponent(nu, inv_T)) * R * R / (D10pc * D10pc);
+    return F > 0 ? -2.5 * log10(F) + (-48.6) : dinf();
+}
+
 // ---------------------------------------------------------------------------
 // theta column -> physical scalar (nmma/core/conversion.py:119-126, em/model.py:272-286)
 // ---------------------------------------------------------------------------

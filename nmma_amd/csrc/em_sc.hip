@@ -105,17 +105,12 @@ __global__ __launch_bounds__(256) void piro2021_lc(const EmDev* __restrict__ Pp,
             const int rf = i / nch, jj = i - rf * nch;
             const int r = rf / M, f = rf - r * M;
             const double nu = P.nu0[f] * scal[r * NSCAL + 4];
-            double ex = h_cgs * nu * inv_t[r * NCH + jj] / kb;
-            if (ex > 700) ex = 700;        // np.clip(., None, 700); NaN passes through
             const double R = rph[r * NCH + jj];
             double F, mag;
             if (PROBE == 2) {
-                F = ex * R;
+                F = bb_exponent(nu, inv_t[r * NCH + jj]) * R;
                 mag = F;
-            } else {
-                F = 2.0 * h_cgs / (c_cgs * c_cgs) * (nu * nu * nu) / expm1(ex) * R * R / (D10pc * D10pc);
-                mag = F > 0 ? -2.5 * log10(F) + (-48.6) : dinf();
-            }
+            } else mag = bb_abs_mag(nu, inv_t[r * NCH + jj], R, F);
             const bool pos = F > 0;
             if (PROBE != 1 || mag == 12345.678) lc[((b0 + r) * M + f) * NS + j0 + jj] = mag;
             // count the positive fluxes: the wave's lanes mostly share one (row, filter) -- one atomic for them, one each for the rest

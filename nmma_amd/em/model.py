@@ -307,7 +307,7 @@ def create_light_curve_model_from_args(em_transient, args, filters=None, sample_
     -> an :class:`ExternalLightCurveModel` around that object's ``generate_lightcurve`` (a model whose arithmetic is third-party
     code and stays on the host: the reference's ``GRBLightCurveModel`` for ``TrPi2018``, its supernova / shock-cooling / host-galaxy
     models); a name in ``device_models`` that the device can build (``DEVICE_MODEL_CLASSES``: ``Piro2021`` -> the shock-cooling
-    model's own kernel) needs no host object; anything else is an SVD surrogate, as in the reference's own fall-through
+    model's own kernel, ``HoNa2020`` -> the Hotokezaka & Nakar kilonova's) needs no host object; anything else is an SVD surrogate, as in the reference's own fall-through
     (model.py:1585-1587)."""
     from . import utils
     names = em_transient.split(",") if isinstance(em_transient, str) else list(em_transient)
@@ -394,19 +394,31 @@ class _TensorModelMixin:
 
 class SimpleKilonovaLightCurveModel(_TensorModelMixin, LightCurveModelContainer):
     """Analytic kilonova models on the GPU (reference: model.py:1280-1337).  ``Me2017``
-    (lightcurve_generation.py:566-652) is implemented; the explicit-Euler layer model runs
-    one wave per parameter vector (``me2017_lc``)."""
+    (lightcurve_generation.py:566-652): the explicit-Euler layer model runs one wave per parameter vector (``me2017_lc``).
+    ``HoNa2020`` (:654-771): the Hotokezaka & Nakar shells, integrated by scipy's adaptive RK45 one wave per parameter vector
+    (``hona2020_lc``); times are days outside and seconds inside, and the caller's ``sample_times`` are never written to (the
+    reference's wiring of this model does not run: DEVIATIONS.md)."""
 
     gpu_model_kind = "me2017"
+    PARAMETERS = {"Me2017": ["log10_mej", "log10_vej", "beta", "log10_kappa_r"],
+                  "HoNa2020": ["log10_mej", "vej_max", "vej_min", "vej_frac", "log10_kappa_low_vej", "log10_kappa_high_vej"]}
 
     def __init__(self, model="Me2017", filters=None, sample_times=None, filter_lambdas=None, cosmo_grid=None,
                  device=0, **em_model_kwargs):
-        if model != "Me2017":
-            raise ValueError("nmma_amd implements the Me2017 analytic model only")
-        mp = ["log10_mej", "log10_vej", "beta", "log10_kappa_r"]
-        super().__init__(model, filters, mp, sample_times)
-        if np.any(np.asarray(self.model_times) == 0):
+        if model not in self.PARAMETERS:
+            raise ValueError("nmma_amd implements the Me2017 and HoNa2020 analytic models only")
+        self.gpu_model_kind = model.lower()
+        super().__init__(model, filters, list(self.PARAMETERS[model]), sample_times)
+        st = np.asarray(self.model_times, float)
+        if model == "Me2017" and np.any(st == 0):
             raise ValueError("For Me2017, start later than t=0")
+        if model == "HoNa2020":
+            if st.ndim != 1 or len(st) < 2 or not np.all(np.diff(st) > 0):
+                raise ValueError("HoNa2020: sample_times must be at least two strictly ascending times")
+            if st[0] < 5e-2:
+                raise ValueError("HoNa2020 model is only valid for times >= 0.05 days")
+            if not st[-1] * 86400.0 - st[0] * 86400.0 > 5e-2 * 86400.0:
+                raise ValueError("HoNa2020: sample_times must span more than the integrator's first step of 0.05 days")
         lam = dict(BUILTIN_FILTER_LAMBDAS)
         lam.update(filter_lambdas or {})
         missing = [f for f in self.filters if f not in lam]
@@ -417,6 +429,10 @@ class SimpleKilonovaLightCurveModel(_TensorModelMixin, LightCurveModelContainer)
         self.filter_nu0 = dict(zip(self.filters, self.nu_0s))
         self.cosmo_grid, self.device = cosmo_grid, device
         self._lc_engine, self._lc_names = None, None
+
+    def setup_model_times(self, tmin=0.01, tmax=14.0, nsteps=150):
+        """model.py:1316-1318: HoNa2020 starts at 0.05 d; Me2017 keeps the container's grid."""
+        return super().setup_model_times(5e-2 if self.model == "HoNa2020" else tmin, tmax, nsteps)
 
     def gen_detector_lc(self, parameters=None, sample_times=None):
         import torch
@@ -530,7 +546,7 @@ class SimpleBolometricLightCurveModel(LightCurveModelContainer):
 
 
 #: names of ``HOST_ONLY_MODELS`` the device can build when the caller asks for them (``device_models=`` of the factory)
-DEVICE_MODEL_CLASSES = {"Piro2021": ShockCoolingLightCurveModel}
+DEVICE_MODEL_CLASSES = {"Piro2021": ShockCoolingLightCurveModel, "HoNa2020": SimpleKilonovaLightCurveModel}
 
 
 class ExternalLightCurveModel(_TensorModelMixin, LightCurveModelContainer):

@@ -120,8 +120,9 @@ class EMEngine:
         # "svd_gp": the SVD model with the Gaussian-process surrogate -- an external-kind handle (theta layout, sample_times, the
         # likelihood from curves) next to an nmma_gp_handle that evaluates the curves (one launch each)
         # "piro2021": the shock-cooling model, closed form per node (kernel piro2021_lc), served like "me2017"
+        # "hona2020": the Hotokezaka & Nakar kilonova, an adaptive RK45 integration per row (kernel hona2020_lc), served like "me2017"
         kinds = {"svd": L.MODEL_SVD, "me2017": L.MODEL_ME2017, "external": L.MODEL_EXTERNAL, "svd_gp": L.MODEL_EXTERNAL,
-                 "piro2021": L.MODEL_PIRO2021}
+                 "piro2021": L.MODEL_PIRO2021, "hona2020": L.MODEL_HONA2020}
         if model_kind not in kinds:
             raise L.NMMAHipError(f"unknown model_kind {model_kind!r}")
         self.model_kind = model_kind
@@ -561,6 +562,16 @@ class EMEngine:
                                                     C.c_void_p(lc.data_ptr()), self._stream()),
                 "nmma_em_model_lightcurves")
         return lc
+
+    def hona_steps(self, theta):
+        """``int32 [B, 2]`` (accepted, rejected) steps of the adaptive integration of every row of a ``"hona2020"`` engine -- what
+        scipy's ``solve_ivp`` takes for the same row (``nmma_em_hona_steps``)."""
+        import torch
+        t = self._dev_theta(theta)
+        out = torch.zeros((t.shape[0], 2), dtype=torch.int32, device=t.device)
+        L.check(self._lib.nmma_em_hona_steps(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0), C.c_void_p(out.data_ptr()),
+                                             self._stream()), "nmma_em_hona_steps")
+        return out
 
     def loglike_lc(self, theta, lc):
         """logL from supplied source-frame light curves lc[B, M, NS] (torch CUDA tensor)."""
