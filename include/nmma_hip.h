@@ -690,6 +690,47 @@ int32_t nmma_bol_loglike_lc(nmma_bol_handle* h, const double* theta_dev, int64_t
 /* "probe": 1 = nmma_bol_loglike without the likelihood phase (measurement: the share of the curve generator); 0 = the kernel */
 int32_t nmma_bol_set_option(nmma_bol_handle* h, const char* name, int32_t value);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Power-law flux light curves: the afterglow-plus-host-galaxy model "Sr2023" (host_lc, nmma/em/lightcurve_generation.py:284-294,
+ * arXiv:2303.12849) and "synchrotron_powerlaw" (:773-783) -- one family, fp64 without contraction (csrc/em_pl.hip):
+ *     F_f(t_j) = A_f * t_j^(-alpha) + C_f,     mag_f(t_j) = -2.5 log10 F_f(t_j) + r_f + s      (flux_to_ABmag, utils.py:793-811)
+ *     Sr2023:       A_f = a_AG_<f>, C_f = f_nu_<f>, r_f = residual_mag[f] (the host magnitude of the filter), s = 0, no extinction
+ *     synchrotron:  A_f = F_ref * (nu0_f (1 + z))^(-beta), C_f = 0, r_f = 16.4 (mJy), s = -distance_modulus(d_L)
+ * A node with F <= 0 or a NaN F is +inf; a (row, filter) with fewer than two positive F is NaN on every node.  An object of its own
+ * next to an nmma_em_handle of kind NMMA_MODEL_EXTERNAL (as nmma_gp_handle is), which supplies sample_times (all > 0), the redshift /
+ * distance / timeshift / extinction slots, filter_nu0 (synchrotron) and the photometry.  The likelihood is ONE launch from theta to
+ * log L without a curve in memory (kernel powerlaw_logl) where the em handle's configuration allows it exactly -- every band observed
+ * through one model filter, constant or one-parameter systematics, no or linear extinction, no sampled Hubble constant, a time grid
+ * of at most NMMA_PL_FUSED_MAX_NS nodes -- and kernel powerlaw_lc followed by nmma_em_loglike_lc otherwise; the choice is made at
+ * nmma_pl_create and reported by nmma_pl_fused. */
+enum nmma_pl_kind { NMMA_PL_SR2023 = 0, NMMA_PL_SYNCHROTRON = 1 };
+#define NMMA_PL_FUSED_MAX_NS 256
+
+typedef struct nmma_pl_config {
+    int32_t abi_version, device;
+    int32_t kind;                    /* enum nmma_pl_kind */
+    int32_t n_filters;               /* M: the em handle's n_model_filters */
+    nmma_slot alpha;                 /* alpha_AG / alpha_time */
+    nmma_slot beta;                  /* beta_freq   (synchrotron; ignored for Sr2023) */
+    nmma_slot f_ref;                 /* F_ref, mJy  (synchrotron; ignored for Sr2023) */
+    const nmma_slot* amp_slots;      /* [M] a_AG_<f>  (Sr2023; NULL for synchrotron) */
+    const nmma_slot* floor_slots;    /* [M] f_nu_<f>  (Sr2023; NULL for synchrotron) */
+    const double* residual_mag;      /* [M] host magnitude per filter, finite and not 0 (Sr2023; NULL for synchrotron) */
+} nmma_pl_config;
+
+typedef struct nmma_pl_handle nmma_pl_handle;
+/* em: the NMMA_MODEL_EXTERNAL handle this object is paired with for its lifetime (every call below must pass the same one). */
+int32_t nmma_pl_create(const nmma_pl_config* cfg, nmma_em_handle* em, nmma_pl_handle** out);
+void nmma_pl_destroy(nmma_pl_handle* pl);
+/* generate_lightcurve: source-frame absolute magnitudes lc_dev[B][M][NS], the contract of nmma_em_model_lightcurves */
+int32_t nmma_pl_model_lightcurves(nmma_pl_handle* pl, nmma_em_handle* em, const double* theta_dev, int64_t B, int64_t ld, double* lc_dev,
+                                  void* stream);
+/* logl_dev[B]: what nmma_em_loglike_lc gives for the curves above (NMMA_LOGL_FLOOR rules included).  Asynchronous on `stream`. */
+int32_t nmma_pl_loglike(nmma_pl_handle* pl, nmma_em_handle* em, const double* theta_dev, int64_t B, int64_t ld, double* logl_dev,
+                        void* stream);
+/* 1: nmma_pl_loglike is the one-launch kernel; 0: two launches; -1: bad arguments */
+int32_t nmma_pl_fused(const nmma_pl_handle* pl, const nmma_em_handle* em);
+
 int32_t nmma_em_profile_begin(nmma_em_handle* h, int32_t max_launches);
 int32_t nmma_em_profile_end(nmma_em_handle* h, double* fused_ms_total, double* combine_ms_total,
                             int32_t* n_launches);

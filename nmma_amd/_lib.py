@@ -19,14 +19,14 @@ SRC_PATH = os.path.join(_HERE, "csrc", "em_kernels.hip")
 #: critical path).  Order = this machine's unit times, longest first (tools: _lib.UNIT_SECONDS after a forced build).
 SOURCES = ("em_kernels.hip", "em_lc64.hip", "em_lc.hip", "em_logl_w3.hip", "em_logl_w2.hip", "em_logl_wc1.hip", "em_logl_w1.hip", "em_logl_f5.hip", "em_logl_f02.hip",
            "em_logl_w4.hip", "em_logl_wc2.hip", "em_logl_w5.hip", "em_logl_f8.hip", "em_logl_f6.hip", "em_logl_f9.hip", "em_logl_f4.hip", "em_logl_f3.hip", "em_logl_f7.hip",
-           "gw_kernels.hip", "em_logl_f1.hip", "walk_kernels.hip", "em_gp.hip", "em_sc.hip", "em_bol.hip", "em_kn.hip")
+           "gw_kernels.hip", "em_logl_f1.hip", "walk_kernels.hip", "em_gp.hip", "em_sc.hip", "em_bol.hip", "em_kn.hip", "em_pl.hip")
 #: per-unit flags after the common ones.  The EM unit keeps -ffp-contract=off (the reference's numpy expressions are not fused and
 #: the parity tests compare bit patterns of intermediate results); the GW unit has no bit-level counterpart (its reference
 #: arithmetic is third-party and absent) and lets hipcc fuse multiply-adds: a quarter fewer instructions in the bin loop.
-# The GP, shock-cooling, bolometric and kilonova-integrator units (fp64 only) are kept clear of packed-fp32 instruction selection.
+# The GP, shock-cooling, bolometric, kilonova-integrator and power-law units (fp64 only) are kept clear of packed-fp32 instruction selection.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"gw_kernels.hip": ["-ffp-contract=fast"], "em_gp.hip": _NO_PACKED_FP32, "em_sc.hip": _NO_PACKED_FP32, "em_bol.hip": _NO_PACKED_FP32,
-              "em_kn.hip": _NO_PACKED_FP32}
+              "em_kn.hip": _NO_PACKED_FP32, "em_pl.hip": _NO_PACKED_FP32}
 
 #: seconds each unit took in this process's last build_library call (tools: order SOURCES longest first)
 UNIT_SECONDS = {}
@@ -47,6 +47,8 @@ SYS_CONST, SYS_PARAM, SYS_NODES = range(3)
 MODEL_SVD, MODEL_ME2017, MODEL_EXTERNAL, MODEL_PIRO2021, MODEL_HONA2020 = range(5)
 EXT_LINEAR, EXT_P92_SMC_HOST = range(2)
 BOL_SUPPLIED, BOL_ARNETT, BOL_ARNETT_MODIFIED = range(3)
+PL_SR2023, PL_SYNCHROTRON = range(2)
+PL_FUSED_MAX_NS = 256
 
 
 class NMMAHipError(RuntimeError):
@@ -117,6 +119,15 @@ class BolConfig(C.Structure):
         ("tau_m", Slot), ("log10_mni", Slot), ("t_0", Slot), ("timeshift", Slot), ("redshift", Slot), ("luminosity_distance", Slot),
         ("em_syserr", Slot),
         ("redshift_mode", C.c_int32), ("n_cosmo", C.c_int32), ("dist_grid", _pd), ("z_grid", _pd),
+    ]
+
+
+class PlConfig(C.Structure):
+    """Mirror of ``struct nmma_pl_config`` (field order must match the header)."""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("device", C.c_int32), ("kind", C.c_int32), ("n_filters", C.c_int32),
+        ("alpha", Slot), ("beta", Slot), ("f_ref", Slot),
+        ("amp_slots", C.POINTER(Slot)), ("floor_slots", C.POINTER(Slot)), ("residual_mag", _pd),
     ]
 
 
@@ -243,6 +254,11 @@ PROTOTYPES = {
     "nmma_bol_model_lightcurves": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nmma_bol_loglike_lc": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nmma_bol_set_option": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_int32]),
+    "nmma_pl_create": (C.c_int32, [C.POINTER(PlConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "nmma_pl_destroy": (None, [C.c_void_p]),
+    "nmma_pl_model_lightcurves": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nmma_pl_loglike": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nmma_pl_fused": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "nmma_em_loglike_lc_parts": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nmma_em_lightcurves_lc": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nmma_em_check": (C.c_int32, [C.c_void_p]),

@@ -307,7 +307,7 @@ def create_light_curve_model_from_args(em_transient, args, filters=None, sample_
     -> an :class:`ExternalLightCurveModel` around that object's ``generate_lightcurve`` (a model whose arithmetic is third-party
     code and stays on the host: the reference's ``GRBLightCurveModel`` for ``TrPi2018``, its supernova / shock-cooling / host-galaxy
     models); a name in ``device_models`` that the device can build (``DEVICE_MODEL_CLASSES``: ``Piro2021`` -> the shock-cooling
-    model's own kernel, ``HoNa2020`` -> the Hotokezaka & Nakar kilonova's) needs no host object; anything else is an SVD surrogate, as in the reference's own fall-through
+    model's own kernel, ``HoNa2020`` -> the Hotokezaka & Nakar kilonova's, ``Sr2023`` -> the afterglow-plus-host-galaxy power law's) needs no host object; anything else is an SVD surrogate, as in the reference's own fall-through
     (model.py:1585-1587)."""
     from . import utils
     names = em_transient.split(",") if isinstance(em_transient, str) else list(em_transient)
@@ -545,8 +545,74 @@ class SimpleBolometricLightCurveModel(LightCurveModelContainer):
         return self._curves(_with_host_redshift(parameters, self.cosmo_grid), sample_times, detector=True)
 
 
+class PowerLawFluxLightCurveModel(_TensorModelMixin, LightCurveModelContainer):
+    """Power-law flux models on the GPU: ``Sr2023`` -- afterglow plus host galaxy, arXiv:2303.12849 (reference:
+    ``HostGalaxyLightCurveModel``, model.py:1014-1058; ``host_lc``, lightcurve_generation.py:284-294) -- and ``synchrotron_powerlaw``
+    (:773-783, the reference's ``SimpleKilonovaLightCurveModel("synchrotron_powerlaw")``).  Per filter ``F = A_f t^(-alpha) + C_f`` and
+    ``flux_to_ABmag``; kernel ``powerlaw_logl`` takes theta to log L in one launch, ``powerlaw_lc`` writes the curves.
+
+    ``Sr2023``: ``model_parameters`` follow the filters -- ``alpha_AG``, then ``a_AG_<f>`` per filter, then ``f_nu_<f>`` per filter
+    (fluxes in muJy); ``host_mag`` is a float or one per filter, never 0; extinction is implicit in the host model and not applied.
+    The reference's class wiring of this model does not run (DEVIATIONS.md); the arithmetic of ``host_lc`` is what is reproduced."""
+
+    gpu_model_kind = "powerlaw"
+    MODELS = ("Sr2023", "synchrotron_powerlaw")
+
+    def __init__(self, model="Sr2023", filters=None, sample_times=None, host_mag=23.9, filter_lambdas=None, cosmo_grid=None,
+                 device=0, **em_model_kwargs):
+        if model not in self.MODELS:
+            raise ValueError(f"PowerLawFluxLightCurveModel: model is one of {self.MODELS}")
+        if isinstance(filters, str):
+            filters = filters.split(",")
+        if not filters:
+            raise ValueError(f"{model}: the filters of the photometry are needed (the parameters and the magnitudes are per filter)")
+        filters = list(filters)
+        if model == "Sr2023":
+            parameters = ["alpha_AG"] + [f"a_AG_{f}" for f in filters] + [f"f_nu_{f}" for f in filters]
+        else:
+            parameters = ["alpha_time", "beta_freq", "F_ref", "luminosity_distance"]      # (model.py:71)
+        super().__init__(model, filters, parameters, sample_times)
+        st = np.asarray(self.model_times, float)
+        if st.ndim != 1 or len(st) < 2 or not np.all(np.diff(st) > 0) or not np.all(st > 0) or not np.all(np.isfinite(st)):
+            raise ValueError(f"{model}: the flux is a power of the time since the trigger: sample_times must be at least two strictly "
+                             "ascending, finite times > 0")
+        self.host_mag = None
+        if model == "Sr2023":
+            hm = np.asarray(host_mag, dtype=float)
+            if hm.ndim > 1 or (hm.ndim == 1 and len(hm) != len(filters)):
+                raise ValueError("Sr2023: host_mag is a float or one value per filter")
+            hm = np.broadcast_to(hm, (len(filters),)).copy()
+            if not np.all(np.isfinite(hm)) or np.any(hm == 0):
+                # (flux_to_ABmag tests `if residual_mag:` -- 0 would silently become the cgs zero point -48.6)
+                raise ValueError("Sr2023: host_mag must be finite and not 0 (the reference reads a host magnitude of 0 as 'none given')")
+            self.host_mag = hm
+            self.ebv_coeff = {f: 0.0 for f in filters}        # extinction is implicit in the host-galaxy model (model.py:1057)
+        else:
+            lam = dict(BUILTIN_FILTER_LAMBDAS)
+            lam.update(filter_lambdas or {})
+            missing = [f for f in filters if f not in lam]
+            if missing:
+                raise ValueError(f"effective wavelengths needed for filters {missing} (pass filter_lambdas)")
+            self.lambdas = np.array([lam[f] for f in filters])
+            self.nu_0s = C_SI / self.lambdas
+            self.filter_nu0 = dict(zip(filters, self.nu_0s))
+        self.cosmo_grid, self.device = cosmo_grid, device
+        self._lc_engine, self._lc_names = None, None
+
+    def engine_kwargs(self):
+        kw = super().engine_kwargs()
+        kw["powerlaw"] = dict(model=self.model, host_mag=self.host_mag)
+        return kw
+
+    gen_detector_lc = SimpleKilonovaLightCurveModel.gen_detector_lc
+
+
+#: the reference's name of the Sr2023 class (model.py:1014)
+HostGalaxyLightCurveModel = PowerLawFluxLightCurveModel
+
 #: names of ``HOST_ONLY_MODELS`` the device can build when the caller asks for them (``device_models=`` of the factory)
-DEVICE_MODEL_CLASSES = {"Piro2021": ShockCoolingLightCurveModel, "HoNa2020": SimpleKilonovaLightCurveModel}
+DEVICE_MODEL_CLASSES = {"Piro2021": ShockCoolingLightCurveModel, "HoNa2020": SimpleKilonovaLightCurveModel,
+                        "Sr2023": PowerLawFluxLightCurveModel}
 
 
 class ExternalLightCurveModel(_TensorModelMixin, LightCurveModelContainer):

@@ -99,13 +99,16 @@ class EMEngine:
     ebv_coeff : dict model filter -> A_filter / E(B-V), or None (linear law: ext_mag = coeff * Ebv)
     extinction_law : None / "linear" (``ebv_coeff``) or "P92_SMC_host" (Pei 1992 SMC curve at every sample's
         host-frame wavelength, utils.py:373-428; needs ``filter_nu0``: dict model filter -> Hz)
+    powerlaw : ``model_kind="powerlaw"`` only: dict(model="Sr2023" | "synchrotron_powerlaw", host_mag=[M] for Sr2023);
+        ``model_parameters`` are then the model's names (Sr2023: ``alpha_AG``, ``a_AG_<f>`` ..., ``f_nu_<f>`` ...; synchrotron:
+        ``alpha_time, beta_freq, F_ref``), each sampled or fixed; ``filter_nu0`` is needed for the synchrotron model
     """
 
     def __init__(self, svd_model, model_filters, model_parameters, parameter_names, fixed=None,
                  sample_times=None, cosmo_grid=None, data=None, observed_filters=(), sources=None,
                  detection_limit=None, systematics=None, ebv_coeff=None, device=0, n_coeff=None,
                  model_kind="svd", filter_nu0=None, extinction_law=None, hubble_reference=None, stack_operands=0, base_times=None,
-                 null_filters=()):
+                 null_filters=(), powerlaw=None):
         self._handle = None
         self._host_out = {}
         lib = L.load_library()
@@ -121,13 +124,22 @@ class EMEngine:
         # likelihood from curves) next to an nmma_gp_handle that evaluates the curves (one launch each)
         # "piro2021": the shock-cooling model, closed form per node (kernel piro2021_lc), served like "me2017"
         # "hona2020": the Hotokezaka & Nakar kilonova, an adaptive RK45 integration per row (kernel hona2020_lc), served like "me2017"
+        # "powerlaw": Sr2023 / synchrotron_powerlaw -- an external-kind handle next to an nmma_pl_handle (kernels powerlaw_lc / powerlaw_logl);
+        # its parameters live in the side handle's slots (Sr2023 has 2 M + 1 of them), so the em handle carries none
         kinds = {"svd": L.MODEL_SVD, "me2017": L.MODEL_ME2017, "external": L.MODEL_EXTERNAL, "svd_gp": L.MODEL_EXTERNAL,
-                 "piro2021": L.MODEL_PIRO2021, "hona2020": L.MODEL_HONA2020}
+                 "piro2021": L.MODEL_PIRO2021, "hona2020": L.MODEL_HONA2020, "powerlaw": L.MODEL_EXTERNAL}
         if model_kind not in kinds:
             raise L.NMMAHipError(f"unknown model_kind {model_kind!r}")
         self.model_kind = model_kind
-        self._gp = None
+        self._gp = self._pl = None
         gp_cfg = None
+        pl_parameters = ()
+        if model_kind == "powerlaw":
+            if not powerlaw or powerlaw.get("model") not in ("Sr2023", "synchrotron_powerlaw"):
+                raise L.NMMAHipError("model_kind 'powerlaw' needs powerlaw=dict(model='Sr2023' | 'synchrotron_powerlaw', ...)")
+            if powerlaw["model"] == "synchrotron_powerlaw" and filter_nu0 is None:
+                raise L.NMMAHipError("synchrotron_powerlaw needs filter_nu0 (observer-frame filter frequencies, Hz)")
+            pl_parameters, model_parameters = list(model_parameters), []
         if model_kind == "svd_gp":
             gp_cfg, gp_keep, n_c, n_t = self._gp_config(svd_model, model_filters, model_parameters, n_coeff)
             if sample_times is None:
@@ -340,6 +352,35 @@ class EMEngine:
             L.check(lib.nmma_gp_create(C.byref(gp_cfg), C.byref(g)), "nmma_gp_create")
             self._gp = g
             del gp_keep
+        if model_kind == "powerlaw":
+            self._pl_create(lib, powerlaw, pl_parameters, names, fixed)
+
+    def _pl_create(self, lib, spec, parameters, names, fixed):
+        """The ``nmma_pl_handle`` next to the external-kind handle: every parameter a slot (sampled, fixed, or a log10_ alias)."""
+        slot = lambda key: resolve_model_param_slot(key, names, fixed)
+        m = len(self.model_filters)
+        cfg = L.PlConfig()
+        cfg.abi_version, cfg.device, cfg.n_filters = L.ABI_VERSION, self.device, m
+        if spec["model"] == "Sr2023":
+            if len(parameters) != 2 * m + 1:
+                raise L.NMMAHipError("Sr2023 takes alpha_AG, then a_AG_<f> per filter, then f_nu_<f> per filter")
+            host_mag = _f64(np.broadcast_to(np.asarray(spec.get("host_mag", 23.9), dtype=np.float64), (m,)))
+            amp = (L.Slot * m)(*[slot(k) for k in parameters[1:m + 1]])
+            floor = (L.Slot * m)(*[slot(k) for k in parameters[m + 1:]])
+            cfg.kind, cfg.alpha = L.PL_SR2023, slot(parameters[0])
+            cfg.beta = cfg.f_ref = L.Slot.constant(0.0)
+            cfg.amp_slots, cfg.floor_slots = C.cast(amp, C.POINTER(L.Slot)), C.cast(floor, C.POINTER(L.Slot))
+            cfg.residual_mag = _ptr(host_mag, C.c_double)
+        else:
+            if len(parameters) < 3:
+                raise L.NMMAHipError("synchrotron_powerlaw takes alpha_time, beta_freq, F_ref")
+            cfg.kind = L.PL_SYNCHROTRON
+            cfg.alpha, cfg.beta, cfg.f_ref = (slot(k) for k in parameters[:3])
+        h = C.c_void_p()
+        L.check(lib.nmma_pl_create(C.byref(cfg), self._handle, C.byref(h)), "nmma_pl_create")
+        self._pl = h
+        #: True: ``loglike`` is the one-launch kernel ``powerlaw_logl``; False: ``powerlaw_lc`` + the likelihood from curves
+        self.powerlaw_fused = bool(lib.nmma_pl_fused(h, self._handle))
 
     @staticmethod
     def _gp_config(svd_model, model_filters, model_parameters, n_coeff):
@@ -376,6 +417,8 @@ class EMEngine:
         return cfg, arrays, n_c, n_t
 
     def _refuse_gp(self, what):
+        if self._pl is not None:
+            raise L.NMMAHipError(f"{what}: not served by a power-law engine (loglike, loglike_parts, lightcurves, model_lightcurves)")
         if self._gp is not None:
             raise L.NMMAHipError(f"{what}: not served by a Gaussian-process engine (model_kind 'svd_gp' evaluates the surrogate and the likelihood "
                                  "in two launches: loglike, loglike_parts, lightcurves, model_lightcurves, coefficients)")
@@ -469,6 +512,15 @@ class EMEngine:
         """logL for every row of ``theta[B, D]``.  torch CUDA tensor in -> torch tensor out
         (asynchronous on ``stream``, default torch's current stream); numpy in -> numpy out (synchronous)."""
         import torch
+        if self._pl is not None:
+            t = self._dev_theta(theta)
+            if out is None:
+                out = torch.empty(t.shape[0], dtype=torch.float64, device=t.device)
+            else:
+                self._check_out(out, t.shape[0])
+            L.check(self._lib.nmma_pl_loglike(self._pl, self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
+                                              C.c_void_p(out.data_ptr()), self._stream(stream)), "nmma_pl_loglike")
+            return out if isinstance(theta, torch.Tensor) else out.cpu().numpy()
         if self._gp is not None:
             t = self._dev_theta(theta)
             if out is None:
@@ -504,11 +556,16 @@ class EMEngine:
         return out
 
     def _gp_curves(self, t, stream=None):
-        """Source-frame curves lc[B, M, NS] of a Gaussian-process engine for the device rows ``t`` (``nmma_gp_model_lightcurves``)."""
+        """Source-frame curves lc[B, M, NS] of a Gaussian-process or power-law engine for the device rows ``t``
+        (``nmma_gp_model_lightcurves`` / ``nmma_pl_model_lightcurves``)."""
         import torch
         lc = torch.empty((t.shape[0], len(self.model_filters), self.n_sample_times), dtype=torch.float64, device=t.device)
         if stream is not None:
             lc.record_stream(stream)
+        if self._pl is not None:
+            L.check(self._lib.nmma_pl_model_lightcurves(self._pl, self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
+                                                        C.c_void_p(lc.data_ptr()), self._stream(stream)), "nmma_pl_model_lightcurves")
+            return lc
         L.check(self._lib.nmma_gp_model_lightcurves(self._gp, self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
                                                     C.c_void_p(lc.data_ptr()), self._stream(stream)), "nmma_gp_model_lightcurves")
         return lc
@@ -520,7 +577,7 @@ class EMEngine:
         n_o = self._n_obs_uploaded            # (incl. the bands without data that stand for unobserved model filters)
         chi = torch.empty((n_o, t.shape[0]), dtype=torch.float64, device=t.device)
         gp = torch.empty_like(chi)
-        if self._gp is not None:
+        if self._gp is not None or self._pl is not None:
             lc = self._gp_curves(t)
             L.check(self._lib.nmma_em_loglike_lc_parts(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0), C.c_void_p(lc.data_ptr()),
                                                        C.c_void_p(chi.data_ptr()), C.c_void_p(gp.data_ptr()), self._stream()),
@@ -539,7 +596,7 @@ class EMEngine:
         ns, m = self.n_sample_times, len(self.model_filters)
         tobs = torch.empty((t.shape[0], ns), dtype=torch.float64, device=t.device)
         mag = torch.empty((t.shape[0], m, ns), dtype=torch.float64, device=t.device)
-        if self._gp is not None:
+        if self._gp is not None or self._pl is not None:
             lc = self._gp_curves(t)
             L.check(self._lib.nmma_em_lightcurves_lc(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0), C.c_void_p(lc.data_ptr()),
                                                      C.c_void_p(tobs.data_ptr()), C.c_void_p(mag.data_ptr()), self._stream()),
@@ -554,7 +611,7 @@ class EMEngine:
         """Source-frame absolute magnitudes lc[B, M, NS] of the handle's model (generate_lightcurve)."""
         import torch
         t = self._dev_theta(theta)
-        if self._gp is not None:
+        if self._gp is not None or self._pl is not None:
             return self._gp_curves(t)
         lc = torch.empty((t.shape[0], len(self.model_filters), self.n_sample_times), dtype=torch.float64,
                          device=t.device)
@@ -796,6 +853,9 @@ class EMEngine:
         if getattr(self, "_gp", None):
             self._lib.nmma_gp_destroy(self._gp)
             self._gp = None
+        if getattr(self, "_pl", None):
+            self._lib.nmma_pl_destroy(self._pl)
+            self._pl = None
         if getattr(self, "_handle", None):
             self._lib.nmma_em_destroy(self._handle)
             self._handle = None
