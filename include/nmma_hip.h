@@ -636,6 +636,46 @@ int32_t nmma_gp_coefficients(nmma_gp_handle* gp, nmma_em_handle* em, const doubl
 int32_t nmma_gp_model_lightcurves(nmma_gp_handle* gp, nmma_em_handle* em, const double* theta_dev, int64_t B, int64_t ld, double* lc_dev,
                                   void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Surrogates of the SVD model whose network has several hidden layers (nmma/em/lightcurve_generation.py:180-217 calls whatever Keras
+ * model the file holds; the reference's training tutorial builds 6 -> 64 -> 128 -> 64 -> 10).  An object of its own next to an
+ * nmma_em_handle of kind NMMA_MODEL_EXTERNAL, as nmma_gp_handle is.  For filter m, with x = (theta_model - param_mins) / (param_maxs -
+ * param_mins) formed in fp64 and rounded once to fp32:
+ *     h_l = relu(W_l^T h_{l-1} + b_l), l = 1 .. L_m;   c = W_out^T h_L + b_out        exact fp32 FMAs (v_mfma_f32_16x16x4_f32)
+ * One output is four chains over interleaved input units (chain 0 starts from the bias) added as (s0 + s1) + (s2 + s3): the order
+ * depends on the layer's shape alone, so a row's bits depend on nothing but its own theta.  Filters may have different architectures.
+ * Limits: 1 .. NMMA_MLP_MAX_HIDDEN hidden layers, each 1 .. 512 wide (any width: zero padding to 16 is exact); relu only. */
+#define NMMA_MLP_MAX_HIDDEN 6
+typedef struct nmma_mlp_config {
+    int32_t abi_version, device;
+    int32_t n_model_filters, n_params, n_coeff, n_tt;
+    const int32_t* n_layers;        /* [M] hidden layers L_m */
+    const int32_t* widths;          /* [M][NMMA_MLP_MAX_HIDDEN] hidden widths H_1 .. H_L (the rest ignored) */
+    const float* weights;           /* filter m at weight_offsets[m]: W_1 [NP][H_1], W_2 [H_1][H_2], ..., W_out [H_L][NC], row-major (Keras kernels) */
+    const int64_t* weight_offsets;  /* [M] in floats */
+    const float* biases;            /* filter m at bias_offsets[m]: b_1 [H_1], ..., b_out [NC] */
+    const int64_t* bias_offsets;    /* [M] in floats */
+    const double* VA;               /* [M][NT][NC] */
+    const double* mins;             /* [M][NT] */
+    const double* maxs;             /* [M][NT] */
+    const double* tt;               /* [M][NT] */
+    const double* param_mins;       /* [M][NP] */
+    const double* param_maxs;       /* [M][NP] */
+} nmma_mlp_config;
+
+typedef struct nmma_mlp_handle nmma_mlp_handle;
+/* Refuses, naming the filter, the layer and the limit, what the kernel cannot hold; nothing is approximated. */
+int32_t nmma_mlp_create(const nmma_mlp_config* cfg, nmma_mlp_handle** out);
+void nmma_mlp_destroy(nmma_mlp_handle* mlp);
+
+/* coeff_dev[B][M][NC] fp64: the network's fp32 outputs, widened.  em: a handle with mlp's n_params on mlp's device. */
+int32_t nmma_mlp_coefficients(nmma_mlp_handle* mlp, nmma_em_handle* em, const double* theta_dev, int64_t B, int64_t ld, double* coeff_dev,
+                              void* stream);
+/* lc_dev[B][M][NS]: source-frame absolute magnitudes on em's sample_times, +inf outside tt; em must list mlp's n_model_filters.  One
+ * launch; the likelihood is a second one (nmma_em_loglike_lc). */
+int32_t nmma_mlp_model_lightcurves(nmma_mlp_handle* mlp, nmma_em_handle* em, const double* theta_dev, int64_t B, int64_t ld, double* lc_dev,
+                                   void* stream);
+
 /* The remaining outputs of the likelihood-from-curves path for SUPPLIED source-frame curves lc_dev[B][M][NS]: the per-filter pieces
  * of nmma_em_loglike_parts, and the detector-frame curves of nmma_em_lightcurves (gen_detector_lc's tail, model.py:381-404). */
 int32_t nmma_em_loglike_lc_parts(nmma_em_handle* h, const double* theta_dev, int64_t B, int64_t ld, const double* lc_dev,

@@ -19,13 +19,13 @@ SRC_PATH = os.path.join(_HERE, "csrc", "em_kernels.hip")
 #: critical path).  Order = this machine's unit times, longest first (tools: _lib.UNIT_SECONDS after a forced build).
 SOURCES = ("em_kernels.hip", "em_lc64.hip", "em_lc.hip", "em_logl_w3.hip", "em_logl_w2.hip", "em_logl_wc1.hip", "em_logl_w1.hip", "em_logl_f5.hip", "em_logl_f02.hip",
            "em_logl_w4.hip", "em_logl_wc2.hip", "em_logl_w5.hip", "em_logl_f8.hip", "em_logl_f6.hip", "em_logl_f9.hip", "em_logl_f4.hip", "em_logl_f3.hip", "em_logl_f7.hip",
-           "gw_kernels.hip", "em_logl_f1.hip", "walk_kernels.hip", "em_gp.hip", "em_sc.hip", "em_bol.hip", "em_kn.hip", "em_pl.hip")
+           "gw_kernels.hip", "em_logl_f1.hip", "walk_kernels.hip", "em_mlp.hip", "em_gp.hip", "em_sc.hip", "em_bol.hip", "em_kn.hip", "em_pl.hip")
 #: per-unit flags after the common ones.  The EM unit keeps -ffp-contract=off (the reference's numpy expressions are not fused and
 #: the parity tests compare bit patterns of intermediate results); the GW unit has no bit-level counterpart (its reference
 #: arithmetic is third-party and absent) and lets hipcc fuse multiply-adds: a quarter fewer instructions in the bin loop.
 # The GP, shock-cooling, bolometric, kilonova-integrator and power-law units (fp64 only) are kept clear of packed-fp32 instruction selection.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-UNIT_FLAGS = {"gw_kernels.hip": ["-ffp-contract=fast"], "em_gp.hip": _NO_PACKED_FP32, "em_sc.hip": _NO_PACKED_FP32, "em_bol.hip": _NO_PACKED_FP32,
+UNIT_FLAGS = {"gw_kernels.hip": ["-ffp-contract=fast"], "em_gp.hip": _NO_PACKED_FP32, "em_mlp.hip": _NO_PACKED_FP32, "em_sc.hip": _NO_PACKED_FP32, "em_bol.hip": _NO_PACKED_FP32,
               "em_kn.hip": _NO_PACKED_FP32, "em_pl.hip": _NO_PACKED_FP32}
 
 #: seconds each unit took in this process's last build_library call (tools: order SOURCES longest first)
@@ -37,6 +37,7 @@ STACK2_COMPLETED = 2
 MAX_PARAMS = 8
 MAX_COEFF = 16
 MAX_SOURCES = 3
+MLP_MAX_HIDDEN = 6
 LOGL_FLOOR = -1.7976931348623157e308
 
 OP_IDENT, OP_RAD2DEG, OP_DEG2RAD, OP_LOG10, OP_POW10, OP_THETAJN2DEG, OP_COSTHETAJN2DEG, OP_ACOS = range(8)
@@ -105,6 +106,17 @@ class GpConfig(C.Structure):
         ("n_model_filters", C.c_int32), ("n_params", C.c_int32), ("n_coeff", C.c_int32), ("n_tt", C.c_int32),
         ("n_train", _pi), ("X", _pd), ("alpha", _pd),
         ("constant", _pd), ("length_scale", _pd), ("rq_alpha", _pd), ("y_mean", _pd), ("y_std", _pd),
+        ("VA", _pd), ("mins", _pd), ("maxs", _pd), ("tt", _pd), ("param_mins", _pd), ("param_maxs", _pd),
+    ]
+
+
+class MlpConfig(C.Structure):
+    """Mirror of ``struct nmma_mlp_config`` (field order must match the header)."""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("device", C.c_int32),
+        ("n_model_filters", C.c_int32), ("n_params", C.c_int32), ("n_coeff", C.c_int32), ("n_tt", C.c_int32),
+        ("n_layers", _pi), ("widths", _pi), ("weights", _pf), ("weight_offsets", C.POINTER(C.c_int64)),
+        ("biases", _pf), ("bias_offsets", C.POINTER(C.c_int64)),
         ("VA", _pd), ("mins", _pd), ("maxs", _pd), ("tt", _pd), ("param_mins", _pd), ("param_maxs", _pd),
     ]
 
@@ -247,6 +259,10 @@ PROTOTYPES = {
     "nmma_gp_destroy": (None, [C.c_void_p]),
     "nmma_gp_coefficients": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nmma_gp_model_lightcurves": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nmma_mlp_create": (C.c_int32, [C.POINTER(MlpConfig), C.POINTER(C.c_void_p)]),
+    "nmma_mlp_destroy": (None, [C.c_void_p]),
+    "nmma_mlp_coefficients": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nmma_mlp_model_lightcurves": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nmma_bol_create": (C.c_int32, [C.POINTER(BolConfig), C.POINTER(C.c_void_p)]),
     "nmma_bol_destroy": (None, [C.c_void_p]),
     "nmma_bol_loglike": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),

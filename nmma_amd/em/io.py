@@ -1,7 +1,8 @@
 """On-disk formats of the EM path.
 
 * ``save_svd_model`` / ``load_svd_model``: the flat tensor file (one ``.npz``) this
-  framework reads -- ``{filter}/W1,b1,W2,b2,VA,mins,maxs,tt,param_mins,param_maxs,n_coeff``.
+  framework reads -- ``{filter}/W1,b1,W2,b2,VA,mins,maxs,tt,param_mins,param_maxs,n_coeff``; a network with more Dense layers
+  carries ``W3,b3, ...`` as well (the last pair is the linear output layer).
 * ``convert_reference_model``: reads the reference's own layout
   (``{model}.joblib`` + ``{model}[_tf]/{filter}.keras|.h5``, nmma/em/model.py:593-696)
   and writes the flat file: ``.joblib`` through joblib, legacy ``.h5`` networks through h5py or,
@@ -12,6 +13,7 @@
 from __future__ import annotations
 
 import os
+import re
 from datetime import datetime, timezone
 
 import numpy as np
@@ -25,6 +27,20 @@ _GP_KEYS = ("gp_X", "gp_alpha", "gp_const", "gp_ell", "gp_rq_alpha", "gp_ymean",
 _SVD_KEYS = ("VA", "mins", "maxs", "tt", "param_mins", "param_maxs")
 
 
+def dense_chain(tensors):
+    """``[(W1, b1), ..., (Wn, bn)]`` of one filter's tensors: the Dense layers in order, the last one linear."""
+    chain = []
+    while f"W{len(chain) + 1}" in tensors:
+        i = len(chain) + 1
+        chain.append((np.asarray(tensors[f"W{i}"]), np.asarray(tensors[f"b{i}"])))
+    return chain
+
+
+def is_deep_model(svd_model):
+    """True when any filter's network has more than two Dense layers (served by ``EMEngine(model_kind="svd_mlp")``)."""
+    return any("W3" in t for t in svd_model.values())
+
+
 def is_gp_model(svd_model):
     return bool(svd_model) and all("gp_X" in t for t in svd_model.values())
 
@@ -33,7 +49,8 @@ def save_svd_model(path, svd_model, model_parameters=None):
     flat = {}
     for filt, t in svd_model.items():
         n_c = int(t["n_coeff"])
-        for k in (_GP_KEYS + _SVD_KEYS if "gp_X" in t else _KEYS):
+        deep = tuple(f"{c}{i + 1}" for i in range(2, len(dense_chain(t))) for c in "Wb")
+        for k in (_GP_KEYS + _SVD_KEYS if "gp_X" in t else _KEYS + deep):
             a = np.asarray(t[k])
             if k == "VA":
                 a = a[:, :n_c]
@@ -56,9 +73,8 @@ def load_svd_model(path):
             svd.setdefault(filt, {})[key] = z[name]
     for filt, t in svd.items():
         t["n_coeff"] = int(t["n_coeff"])
-        for k in ("W1", "b1", "W2", "b2"):
-            if k in t:
-                t[k] = np.ascontiguousarray(t[k], dtype=np.float32)
+        for k in [k for k in t if re.fullmatch(r"[Wb]\d+", k)]:
+            t[k] = np.ascontiguousarray(t[k], dtype=np.float32)
         for k in _SVD_KEYS + _GP_KEYS:
             if k in t:
                 t[k] = np.ascontiguousarray(t[k], dtype=np.float64)
@@ -144,13 +160,52 @@ def _h5_datasets(path):
     return out
 
 
+def _layer_order_key(name):
+    """Keras numbers its layers ``dense, dense_1, ..., dense_9, dense_10``: the suffix compares as a number, no suffix first."""
+    m = re.fullmatch(r"(.*?)(?:_(\d+))?", name)
+    return m.group(1), -1 if m.group(2) is None else int(m.group(2))
+
+
+def _chain_in_order(named, where):
+    """``named``: ``{layer name: (kernel, bias)}``.  The flat ``(W1, b1, ..., Wn, bn)`` in the order of the layers' names when the
+    shapes chain that way; else in the one order in which they do chain; else a ValueError that lists the shapes."""
+    layers = [named[k] for k in sorted(named, key=_layer_order_key)]
+    if len(layers) < 2:
+        raise ValueError(f"{where}: expected two or more Dense layers, found {len(layers)}")
+    for w, b in layers:
+        if w.ndim != 2 or b.shape != (w.shape[1],):
+            raise ValueError(f"{where}: a Dense layer with kernel {w.shape} and bias {b.shape}")
+    chains = lambda seq: all(seq[i][0].shape[1] == seq[i + 1][0].shape[0] for i in range(len(seq) - 1))
+    if not chains(layers):
+        # depth-first over the orders that chain (a handful of layers): exactly one must exist
+        found = []
+
+        def extend(seq, rest):
+            if not rest:
+                found.append(seq)
+            for i, nxt in enumerate(rest):
+                if len(found) < 2 and (not seq or seq[-1][0].shape[1] == nxt[0].shape[0]):
+                    extend(seq + [nxt], rest[:i] + rest[i + 1:])
+        extend([], layers)
+        if len(found) != 1:
+            raise ValueError(f"{where}: layer shapes do not chain"
+                             + (" in one order only" if found else "") + ": " + ", ".join(str(w.shape) for w, _ in layers))
+        layers = found[0]
+    return tuple(a for layer in layers for a in layer)
+
+
 def _dense_weights_from_h5(path):
-    """(W1, b1, W2, b2) of a Dense -> (Dropout) -> Dense Keras model saved as legacy HDF5
-    (``model_weights/<layer>/<layer>/{kernel,bias}:0``, nmma/em/training.py:353-364; what ``keras.saving.load_model`` reads at
-    nmma/em/model.py:635-648).  The two Dense layers are told apart by their shapes -- the first one's output width is the second
-    one's input width -- not by the order of the group names (``dense_9`` sorts after ``dense_10``)."""
+    """(W1, b1, ..., Wn, bn) of a Keras model of Dense (and Dropout) layers saved as legacy HDF5; see ``_dense_chain``."""
+    return _dense_chain(_h5_datasets(path), path)
+
+
+def _dense_chain(datasets, where):
+    """(W1, b1, ..., Wn, bn) of the Dense layers among ``datasets`` (name -> array) in the legacy HDF5 layout
+    (``[model_weights/]<layer>/<layer>/{kernel,bias}:0``, nmma/em/training.py:353-364; what ``keras.saving.load_model`` reads at
+    nmma/em/model.py:635-648).  The layers are ordered by their names, the numeric suffix compared as a number (``dense_9`` before
+    ``dense_10``), and the shapes must chain; two layers give ``W1, b1, W2, b2`` as before."""
     layers = {}
-    for name, arr in _h5_datasets(path).items():
+    for name, arr in datasets.items():
         parts = name.split("/")
         if parts[0] == "model_weights":          # a full model file (keras model.save): model_weights/<layer>/<layer>/{kernel,bias}:0
             parts = parts[1:]
@@ -159,47 +214,52 @@ def _dense_weights_from_h5(path):
         leaf = parts[-1].split(":")[0]
         if leaf in ("kernel", "bias"):
             layers.setdefault(parts[0], {})[leaf] = np.asarray(arr)
-    dense = [(v["kernel"], v["bias"]) for v in layers.values() if "kernel" in v and "bias" in v]
-    if len(dense) != 2:
-        raise ValueError(f"{path}: expected two Dense layers, found {len(dense)}")
-    if dense[0][0].shape[1] != dense[1][0].shape[0]:
-        dense.reverse()
-    (w1, b1), (w2, b2) = dense
-    if w1.ndim != 2 or w2.ndim != 2 or w1.shape[1] != w2.shape[0] or b1.shape != (w1.shape[1],) or b2.shape != (w2.shape[1],):
-        raise ValueError(f"{path}: layer shapes do not chain: {w1.shape}, {b1.shape}, {w2.shape}, {b2.shape}")
-    return w1, b1, w2, b2
+    return _chain_in_order({k: (v["kernel"], v["bias"]) for k, v in layers.items() if "kernel" in v and "bias" in v}, where)
 
 
 def _dense_pair(datasets, where):
-    """The two Dense layers among ``datasets`` (name -> array): groups that hold exactly one 2-D kernel and one 1-D bias of matching
-    width, ordered by shape chaining."""
+    """(W1, b1, ..., Wn, bn) of the Dense layers among ``datasets`` (name -> array) in a ``.keras`` archive's layout
+    (``layers/<name>/vars/{0,1}``): groups that hold exactly one 2-D kernel and one 1-D bias of matching width, ordered as in
+    ``_dense_chain``."""
     groups = {}
     for name, arr in datasets.items():
         parent = name.rsplit("/", 1)[0] if "/" in name else ""
         groups.setdefault(parent, []).append(np.asarray(arr))
-    dense = []
-    for members in groups.values():
+    dense = {}
+    for parent, members in groups.items():
         if len(members) != 2:
             continue
         k = next((a for a in members if a.ndim == 2), None)
         b = next((a for a in members if a.ndim == 1), None)
         if k is not None and b is not None and b.shape[0] == k.shape[1]:
-            dense.append((k, b))
-    if len(dense) != 2:
-        raise ValueError(f"{where}: expected two Dense layers, found {len(dense)}")
-    if dense[0][0].shape[1] != dense[1][0].shape[0]:
-        dense.reverse()
-    (w1, b1), (w2, b2) = dense
-    if w1.shape[1] != w2.shape[0]:
-        raise ValueError(f"{where}: layer shapes do not chain: {w1.shape}, {w2.shape}")
-    return w1, b1, w2, b2
+            parts = parent.split("/")
+            dense[parts[1] if parts[0] == "layers" and len(parts) > 1 else parent] = (k, b)
+    return _chain_in_order(dense, where)
+
+
+def _check_archive_activations(config, where):
+    """Refuse a ``.keras`` archive whose ``config.json`` names a hidden activation other than relu or a non-linear output: the device
+    kernels evaluate relu hidden layers and a linear output, nothing else."""
+    def dense_configs(node):
+        if isinstance(node, dict):
+            if node.get("class_name") == "Dense" and isinstance(node.get("config"), dict):
+                yield node["config"]
+            for v in node.values():
+                yield from dense_configs(v)
+        elif isinstance(node, list):
+            for v in node:
+                yield from dense_configs(v)
+    acts = [c.get("activation") for c in dense_configs(config)]
+    acts = [a.get("config", a.get("class_name")) if isinstance(a, dict) else a for a in acts]
+    if any(a != "relu" for a in acts[:-1]) or (acts and acts[-1] not in ("linear", None)):
+        raise ValueError(f"{where}: Dense activations {acts}; only relu hidden layers and a linear output layer are evaluated")
 
 
 def _dense_weights_from_keras_archive(path):
-    """(W1, b1, W2, b2) of a ``.keras`` archive (Keras 3: a zip holding ``config.json`` and ``model.weights.h5``; what
+    """(W1, b1, ..., Wn, bn) of a ``.keras`` archive (Keras 3: a zip holding ``config.json`` and ``model.weights.h5``; what
     nmma/em/training.py saves today and nmma/em/model.py:635-643 loads first).  With keras importable the model is loaded as the
-    reference does; without it the weights file inside the archive is read directly (h5py or the built-in HDF5 reader) and the two
-    Dense layers are picked by their shapes.  The archive layout (``layers/<name>/vars/{0,1}``) is from Keras' public sources, NOT
+    reference does; without it the weights file inside the archive is read directly (h5py or the built-in HDF5 reader) and the
+    Dense layers are ordered by name and shape; ``config.json``, where readable, must name relu hidden layers and a linear output.  The archive layout (``layers/<name>/vars/{0,1}``) is from Keras' public sources, NOT
     pinned here -- keras is absent from the build image and the reference tree holds no ``.keras`` file."""
     try:
         import keras
@@ -207,8 +267,10 @@ def _dense_weights_from_keras_archive(path):
             raise ImportError("keras is not the real package")
         net = keras.saving.load_model(path, compile=False)
         dense = [l for l in net.layers if l.get_weights()]
-        (w1, b1), (w2, b2) = (l.get_weights() for l in dense)
-        return w1, b1, w2, b2
+        acts = [getattr(getattr(l, "activation", None), "__name__", None) for l in dense]
+        if any(a != "relu" for a in acts[:-1]) or acts[-1] != "linear":
+            raise ValueError(f"{path}: Dense activations {acts}; only relu hidden layers and a linear output layer are evaluated")
+        return tuple(a for l in dense for a in l.get_weights())
     except ImportError:
         pass
     import zipfile
@@ -217,6 +279,13 @@ def _dense_weights_from_keras_archive(path):
         if inner is None:
             raise ValueError(f"{path}: no model.weights.h5 in the archive")
         raw = z.read(inner)
+        try:
+            import json
+            config = json.loads(z.read("config.json"))
+        except (KeyError, ValueError):
+            config = None
+    if config is not None:
+        _check_archive_activations(config, path)
     try:
         import h5py
         if not isinstance(getattr(h5py, "File", None), type):
@@ -243,13 +312,13 @@ def convert_reference_model(svd_path, model, out_path, filters=None, interpolati
     for filt in (filters or list(meta)):
         base = os.path.join(svd_path, f"{model}{spec}", filt.replace(":", "_"))
         if os.path.isfile(base + ".keras"):
-            w1, b1, w2, b2 = _dense_weights_from_keras_archive(base + ".keras")
+            net = _dense_weights_from_keras_archive(base + ".keras")
         elif os.path.isfile(base + ".h5"):
-            w1, b1, w2, b2 = _dense_weights_from_h5(base + ".h5")
+            net = _dense_weights_from_h5(base + ".h5")
         else:
             raise FileNotFoundError(f"no .keras/.h5 network for filter {filt} under {base}")
         m = meta[filt]
-        svd[filt] = dict(W1=np.float32(w1), b1=np.float32(b1), W2=np.float32(w2), b2=np.float32(b2),
+        svd[filt] = dict({f"{'Wb'[i % 2]}{i // 2 + 1}": np.float32(a) for i, a in enumerate(net)},
                          VA=np.asarray(m["VA"], float), mins=np.asarray(m["mins"], float),
                          maxs=np.asarray(m["maxs"], float), tt=np.asarray(m["tt"], float),
                          param_mins=np.asarray(m["param_mins"], float),

@@ -198,6 +198,10 @@ class SVDLightCurveModel(LightCurveModelContainer):
                   n_coeff=self.mag_ncoeff, hubble_reference=getattr(self, "hubble_reference", None))
         if self.interpolation_type == "sklearn_gp":
             kw["model_kind"] = "svd_gp"
+        elif em_io.is_deep_model(self.svd_mag_model):
+            # a filter with more than two Dense layers: the deep-network kernel serves every filter (a two-layer one among them included);
+            # a model whose filters are all two-layer takes the one-launch path as before
+            kw["model_kind"] = "svd_mlp"
         # extinction (get_extinction_mags, model.py:323-342): caller-supplied linear coefficients win; else the
         # default host-frame SMC law is evaluated natively when the filter frequencies are known
         if self.ebv_coeff is None and self.extinction_law == "P92_SMC_host" and self.filter_nu0 is not None:
@@ -800,8 +804,8 @@ class CombinedLightCurveModelContainer(_TensorModelMixin):
         if len(self.lc_models) != 2:
             return None
         for i, m in enumerate(self.lc_models):
-            if not isinstance(m, SVDLightCurveModel) or m.interpolation_type == "sklearn_gp":
-                continue        # (a Gaussian-process surrogate has no one-launch form: its curves are materialised)
+            if not isinstance(m, SVDLightCurveModel) or m.interpolation_type == "sklearn_gp" or em_io.is_deep_model(m.svd_mag_model):
+                continue        # (a Gaussian-process or deep-network surrogate has no one-launch form: its curves are materialised)
             # (the filters the model LISTS: one without a surrogate is its null output -- +inf on every node, "radio and X-ray filters
             #  when using with GRB data", lightcurve_generation.py:168-169 -- and rides along as a null filter of the engine)
             if list(m.filters) == self.filters and len(m.gpu_filters) > 0:

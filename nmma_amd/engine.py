@@ -122,16 +122,20 @@ class EMEngine:
 
         # "svd_gp": the SVD model with the Gaussian-process surrogate -- an external-kind handle (theta layout, sample_times, the
         # likelihood from curves) next to an nmma_gp_handle that evaluates the curves (one launch each)
+        # "svd_mlp": the SVD model whose network has several hidden layers -- the same pairing with an nmma_mlp_handle (kernel mlp_surrogate);
+        # it is served through the Gaussian-process engine's entry points (self._gp holds the handle, self._side names its functions)
         # "piro2021": the shock-cooling model, closed form per node (kernel piro2021_lc), served like "me2017"
         # "hona2020": the Hotokezaka & Nakar kilonova, an adaptive RK45 integration per row (kernel hona2020_lc), served like "me2017"
         # "powerlaw": Sr2023 / synchrotron_powerlaw -- an external-kind handle next to an nmma_pl_handle (kernels powerlaw_lc / powerlaw_logl);
         # its parameters live in the side handle's slots (Sr2023 has 2 M + 1 of them), so the em handle carries none
         kinds = {"svd": L.MODEL_SVD, "me2017": L.MODEL_ME2017, "external": L.MODEL_EXTERNAL, "svd_gp": L.MODEL_EXTERNAL,
+                 "svd_mlp": L.MODEL_EXTERNAL,
                  "piro2021": L.MODEL_PIRO2021, "hona2020": L.MODEL_HONA2020, "powerlaw": L.MODEL_EXTERNAL}
         if model_kind not in kinds:
             raise L.NMMAHipError(f"unknown model_kind {model_kind!r}")
         self.model_kind = model_kind
         self._gp = self._pl = None
+        self._side = "mlp" if model_kind == "svd_mlp" else "gp"
         gp_cfg = None
         pl_parameters = ()
         if model_kind == "powerlaw":
@@ -140,8 +144,9 @@ class EMEngine:
             if powerlaw["model"] == "synchrotron_powerlaw" and filter_nu0 is None:
                 raise L.NMMAHipError("synchrotron_powerlaw needs filter_nu0 (observer-frame filter frequencies, Hz)")
             pl_parameters, model_parameters = list(model_parameters), []
-        if model_kind == "svd_gp":
-            gp_cfg, gp_keep, n_c, n_t = self._gp_config(svd_model, model_filters, model_parameters, n_coeff)
+        if model_kind in ("svd_gp", "svd_mlp"):
+            gp_cfg, gp_keep, n_c, n_t = (self._gp_config if model_kind == "svd_gp" else self._mlp_config)(svd_model, model_filters,
+                                                                                                         model_parameters, n_coeff)
             if sample_times is None:
                 sample_times = np.asarray(svd_model[model_filters[0]]["tt"], dtype=np.float64)
         cfg = L.EmConfig()
@@ -349,7 +354,7 @@ class EMEngine:
         if gp_cfg is not None:
             gp_cfg.abi_version, gp_cfg.device = L.ABI_VERSION, self.device
             g = C.c_void_p()
-            L.check(lib.nmma_gp_create(C.byref(gp_cfg), C.byref(g)), "nmma_gp_create")
+            L.check(getattr(lib, f"nmma_{self._side}_create")(C.byref(gp_cfg), C.byref(g)), f"nmma_{self._side}_create")
             self._gp = g
             del gp_keep
         if model_kind == "powerlaw":
@@ -416,9 +421,51 @@ class EMEngine:
             setattr(cfg, k, _ptr(a, C.c_int32 if k == "n_train" else C.c_double))
         return cfg, arrays, n_c, n_t
 
+    @staticmethod
+    def _mlp_config(svd_model, model_filters, model_parameters, n_coeff):
+        """``nmma_mlp_config`` of a network with several hidden layers: per filter the chain ``W1, b1, ..., Wn, bn`` (Keras kernels,
+        ``[in][out]``; ``nmma_amd.em.io.dense_chain``), the last layer linear.  Filters may differ in depth and widths.  With a network the
+        output width is fixed: ``n_coeff`` must equal it (lightcurve_generation.py:182-198)."""
+        from .em.io import dense_chain
+        first = svd_model[model_filters[0]]
+        chains = [dense_chain(svd_model[f]) for f in model_filters]
+        n_p, n_c, n_t = int(chains[0][0][0].shape[0]), int(chains[0][-1][0].shape[1]), len(first["tt"])
+        if len(model_parameters) != n_p:
+            raise L.NMMAHipError("model_parameters do not match the surrogate input width")
+        if n_coeff and min(int(n_coeff), int(first["n_coeff"])) != n_c:
+            raise L.NMMAHipError("svd_mag_ncoeff must equal the network's output width (nmma/em/lightcurve_generation.py:182-198)")
+        if not 1 <= n_c <= L.MAX_COEFF:
+            raise L.NMMAHipError(f"n_coeff must be 1 .. {L.MAX_COEFF}")
+        widths = np.zeros((len(model_filters), L.MLP_MAX_HIDDEN), dtype=np.int32)
+        for m, (f, chain) in enumerate(zip(model_filters, chains)):
+            if len(chain) < 2 or len(chain) - 1 > L.MLP_MAX_HIDDEN:
+                raise L.NMMAHipError(f"filter {f}: {len(chain) - 1} hidden layers; the kernel serves 1 .. {L.MLP_MAX_HIDDEN}")
+            if chain[0][0].shape[0] != n_p or chain[-1][0].shape[1] != n_c or len(svd_model[f]["tt"]) != n_t:
+                raise L.NMMAHipError(f"filter {f}: input width, output width or time grid differ between filters")
+            widths[m, :len(chain) - 1] = [w.shape[1] for w, _ in chain[:-1]]
+        flat = lambda i: [np.concatenate([_f32(layer[i]).reshape(-1) for layer in chain]) for chain in chains]
+        offsets = lambda parts: np.ascontiguousarray(np.cumsum([0] + [len(a) for a in parts[:-1]]), dtype=np.int64)
+        w_parts, b_parts = flat(0), flat(1)
+        cat = lambda k, cut: _f64(np.concatenate([np.asarray(svd_model[f][k], dtype=np.float64)[cut].reshape(-1) for f in model_filters]))
+        arrays = dict(
+            n_layers=_i32([len(chain) - 1 for chain in chains]), widths=widths,
+            weights=_f32(np.concatenate(w_parts)), weight_offsets=offsets(w_parts),
+            biases=_f32(np.concatenate(b_parts)), bias_offsets=offsets(b_parts),
+            VA=cat("VA", (slice(None), slice(0, n_c))), mins=cat("mins", slice(None)), maxs=cat("maxs", slice(None)), tt=cat("tt", slice(None)),
+            param_mins=cat("param_mins", slice(None)), param_maxs=cat("param_maxs", slice(None)))
+        cfg = L.MlpConfig()
+        cfg.n_model_filters, cfg.n_params, cfg.n_coeff, cfg.n_tt = len(model_filters), n_p, n_c, n_t
+        ctypes_of = {np.dtype(np.int32): C.c_int32, np.dtype(np.int64): C.c_int64, np.dtype(np.float32): C.c_float, np.dtype(np.float64): C.c_double}
+        for k, a in arrays.items():
+            setattr(cfg, k, _ptr(a, ctypes_of[a.dtype]))
+        return cfg, arrays, n_c, n_t
+
     def _refuse_gp(self, what):
         if self._pl is not None:
             raise L.NMMAHipError(f"{what}: not served by a power-law engine (loglike, loglike_parts, lightcurves, model_lightcurves)")
+        if self._gp is not None and self._side == "mlp":
+            raise L.NMMAHipError(f"{what}: not served by a deep-network engine (model_kind 'svd_mlp' evaluates the surrogate and the likelihood "
+                                 "in two launches: loglike, loglike_parts, lightcurves, model_lightcurves, coefficients)")
         if self._gp is not None:
             raise L.NMMAHipError(f"{what}: not served by a Gaussian-process engine (model_kind 'svd_gp' evaluates the surrogate and the likelihood "
                                  "in two launches: loglike, loglike_parts, lightcurves, model_lightcurves, coefficients)")
@@ -566,8 +613,9 @@ class EMEngine:
             L.check(self._lib.nmma_pl_model_lightcurves(self._pl, self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
                                                         C.c_void_p(lc.data_ptr()), self._stream(stream)), "nmma_pl_model_lightcurves")
             return lc
-        L.check(self._lib.nmma_gp_model_lightcurves(self._gp, self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
-                                                    C.c_void_p(lc.data_ptr()), self._stream(stream)), "nmma_gp_model_lightcurves")
+        fn = f"nmma_{self._side}_model_lightcurves"
+        L.check(getattr(self._lib, fn)(self._gp, self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
+                                       C.c_void_p(lc.data_ptr()), self._stream(stream)), fn)
         return lc
 
     def loglike_parts(self, theta):
@@ -736,13 +784,14 @@ class EMEngine:
 
     def coefficients(self, theta):
         """SVD coefficients c[B, M, NC], the surrogate output: fp32 from the network (lightcurve_generation.py:198), fp64 from a
-        Gaussian-process engine (:206-211)."""
+        Gaussian-process engine (:206-211), the network's fp32 values widened to fp64 from a deep-network engine ("svd_mlp")."""
         import torch
         t = self._dev_theta(theta)
         if self._gp is not None:
             c = torch.empty((t.shape[0], len(self.model_filters), self.n_coeff), dtype=torch.float64, device=t.device)
-            L.check(self._lib.nmma_gp_coefficients(self._gp, self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
-                                                   C.c_void_p(c.data_ptr()), self._stream()), "nmma_gp_coefficients")
+            fn = f"nmma_{self._side}_coefficients"
+            L.check(getattr(self._lib, fn)(self._gp, self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
+                                           C.c_void_p(c.data_ptr()), self._stream()), fn)
             return c
         c = torch.empty((t.shape[0], len(self.model_filters), self.n_coeff), dtype=torch.float32, device=t.device)
         L.check(self._lib.nmma_em_coefficients(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0),
@@ -851,7 +900,7 @@ class EMEngine:
             self._lib.nmma_walk_ws_destroy(self._walk_ws)
             self._walk_ws = None
         if getattr(self, "_gp", None):
-            self._lib.nmma_gp_destroy(self._gp)
+            getattr(self._lib, f"nmma_{self._side}_destroy")(self._gp)
             self._gp = None
         if getattr(self, "_pl", None):
             self._lib.nmma_pl_destroy(self._pl)
