@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define NMMA_ABI_VERSION 8
+#define NMMA_ABI_VERSION 9
 #define NMMA_MAX_PARAMS 8      /* surrogate inputs NP (Bu2023Ye: 7; nmma/em/model.py:29-125) */
 #define NMMA_MAX_COEFF 16      /* SVD coefficients NC (reference default 10; em_parsing.py:189) */
 #define NMMA_MAX_SOURCES 3     /* model bands averaged into one observed band (utils.py:549-563) */
@@ -770,6 +770,84 @@ int32_t nmma_pl_loglike(nmma_pl_handle* pl, nmma_em_handle* em, const double* th
                         void* stream);
 /* 1: nmma_pl_loglike is the one-launch kernel; 0: two launches; -1: bad arguments */
 int32_t nmma_pl_fused(const nmma_pl_handle* pl, const nmma_em_handle* em);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Multi-messenger parameter conversion: the step in front of the light curve of a joint GW + EOS + EM analysis
+ * (MultimessengerConversion.basic_cbc, nmma/core/conversion.py:768-824) for a whole batch in ONE launch (kernel mm_convert,
+ * csrc/mm_convert.hip): source-frame masses -> EOS look-up (EOS_to_ns_parameters / EOS_to_system_parameters, :222-237, as
+ * EoSConverter(method="tabulated") drives them, nmma/eos/eos_processing.py:292-360) or the quasi-universal relations
+ * (radii_from_qur, :239-270) -> the NR ejecta fits of KilonovaEjectaFitting (:318-766) with log10_E0 from the disk mass
+ * (grb_energy_conversion, :699-726).  fp64 without contraction, the reference's operation order; a row's bits depend on its own
+ * theta alone.  The derived columns are written behind a copy of the sampled ones, so every other entry point of this library
+ * reads them through plain column slots. */
+enum nmma_mm_mass_mode { NMMA_MM_CHIRP_MASS_RATIO = 0,   /* mass_a = chirp_mass, mass_b = mass_ratio (bilby: generate_component_masses) */
+                         NMMA_MM_COMPONENT_MASSES = 1 }; /* mass_a = mass_1, mass_b = mass_2 */
+enum nmma_mm_eos_mode {
+    NMMA_MM_EOS_TABLES = 0,   /* a sampled EOS index (truncated like astype(int)) picks one of n_eos tables in device memory         */
+    NMMA_MM_EOS_SINGLE = 1,   /* one table, staged once per workgroup in LDS                                                        */
+    NMMA_MM_EOS_QUR = 2,      /* no table: radii and R_16 from the lambda_1 / lambda_2 slots, TOV_mass from its slot                */
+    NMMA_MM_EOS_GIVEN = 3     /* no EOS step: radius_1, radius_2, TOV_mass, R_16 from their slots (the ejecta fits alone)           */
+};
+enum nmma_mm_jet {
+    NMMA_MM_JET_NONE = 0,     /* log10_E0 is not derived (it is sampled, or nobody asks for it)                                     */
+    NMMA_MM_JET_TOPHAT = 1,   /* no thetaWing / alphaWing / b: the closed form, :709                                                */
+    NMMA_MM_JET_POWERLAW = 2  /* b given: scipy.integrate.simpson over the reference's 100 nodes, :298-316 (a Gaussian jet is refused
+                                 by the callers: it needs erf of a complex argument)                                               */
+};
+enum nmma_mm_spin { NMMA_MM_SPIN_CHI = 0,        /* chi_1 from spin_a                                    (:428-429)                  */
+                    NMMA_MM_SPIN_A_COS_TILT = 1, /* spin_a = a_1, spin_b = cos_tilt_1: a_1 * cos_tilt_1 (:431-432)                  */
+                    NMMA_MM_SPIN_A_TILT = 2 };   /* spin_a = a_1, spin_b = tilt_1:     a_1 * cos(tilt_1)                            */
+enum nmma_mm_output {         /* the derived columns, in the order of out_col */
+    NMMA_MM_LOG10_MEJ_DYN = 0, NMMA_MM_LOG10_MEJ_WIND = 1, NMMA_MM_LOG10_MEJ = 2, NMMA_MM_LOG10_E0 = 3, NMMA_MM_LAMBDA_1 = 4,
+    NMMA_MM_LAMBDA_2 = 5, NMMA_MM_RADIUS_1 = 6, NMMA_MM_RADIUS_2 = 7, NMMA_MM_TOV_MASS = 8, NMMA_MM_R_14 = 9, NMMA_MM_R_16 = 10,
+    NMMA_MM_N_OUTPUTS = 11
+};
+#define NMMA_MM_STATUS_EOS_RANGE 1      /* nmma_mm_status: a row's EOS index was outside 0 .. n_eos - 1 (or NaN) */
+#define NMMA_MM_MAX_NODES 1024          /* nodes of one EOS table */
+
+typedef struct nmma_mm_config {
+    int32_t abi_version, device;
+    int32_t n_dim;                      /* D: columns of theta, copied to out[:, 0 .. D) */
+    int32_t mass_mode;                  /* enum nmma_mm_mass_mode */
+    nmma_slot mass_a, mass_b;           /* DETECTOR-frame masses: the source frame is mass / (1 + z), :104-117 */
+    int32_t redshift_mode;              /* enum nmma_redshift_mode: NMMA_Z_ZERO (the masses are source-frame already), NMMA_Z_SLOT, NMMA_Z_GRID */
+    nmma_slot redshift, luminosity_distance;
+    int32_t n_cosmo;                    /* NMMA_Z_GRID: np.interp(d_L; dist_grid, z_grid), constant beyond the ends as nmma_em_config's */
+    const double* dist_grid;            /* [n_cosmo] */
+    const double* z_grid;               /* [n_cosmo] */
+    int32_t eos_mode;                   /* enum nmma_mm_eos_mode */
+    int32_t n_eos;                      /* tables (NMMA_MM_EOS_SINGLE: 1) */
+    const int32_t* eos_n_nodes;         /* [n_eos] 2 .. NMMA_MM_MAX_NODES */
+    const double* eos_radius;           /* the tables one after the other: km                                         */
+    const double* eos_mass;             /* ... solar masses, STRICTLY ASCENDING within a table (else refused, naming it) */
+    const double* eos_log_lambda;       /* ... np.log of the tidal deformability, finite (lambda > 0, else refused).  The CALLER takes the
+                                           logarithm: the reference interpolates np.log(lambdas), and numpy's log is not libm's to the last bit */
+    nmma_slot eos;                      /* NMMA_MM_EOS_TABLES: the sampled index */
+    nmma_slot lambda_1, lambda_2;       /* NMMA_MM_EOS_QUR */
+    nmma_slot tov_mass;                 /* NMMA_MM_EOS_QUR, NMMA_MM_EOS_GIVEN */
+    nmma_slot radius_1, radius_2, r_16; /* NMMA_MM_EOS_GIVEN */
+    int32_t fits;                       /* 1: the ejecta fits run (alpha, ratio_zeta and the spin slots are read); 0: the EOS step alone */
+    nmma_slot alpha, ratio_zeta;
+    int32_t spin_mode;                  /* enum nmma_mm_spin: read by the NSBH branch */
+    nmma_slot spin_a, spin_b;
+    int32_t jet;                        /* enum nmma_mm_jet */
+    nmma_slot ratio_epsilon, theta_core;/* defaults 2e-4 and 0.105, :702-706 */
+    nmma_slot wing;                     /* NMMA_MM_JET_POWERLAW: alphaWing, or thetaWing with wing_is_angle = 1 (alphaWing = thetaWing / thetaCore, :714) */
+    int32_t wing_is_angle;
+    nmma_slot b;
+    int32_t out_col[NMMA_MM_N_OUTPUTS]; /* column of out for every derived quantity (D <= col < ld_out), or -1: not written -- a derived
+                                           key that is itself sampled keeps the sampled value (:326), one the mode does not produce is absent */
+} nmma_mm_config;
+
+typedef struct nmma_mm_handle nmma_mm_handle;
+/* Copies and checks the tables (TOV_mass, R_14 and R_16 per table are formed here, on the host), pads them and uploads. */
+int32_t nmma_mm_create(const nmma_mm_config* cfg, nmma_mm_handle** out);
+void nmma_mm_destroy(nmma_mm_handle* h);
+/* out_dev[B][ld_out] = theta_dev[B][ld] columns 0 .. D) | derived columns.  A row whose EOS index is out of range gets -inf in the four
+ * ejecta columns and 0 in the others, and sets NMMA_MM_STATUS_EOS_RANGE; nothing fails.  Asynchronous on `stream`. */
+int32_t nmma_mm_convert(nmma_mm_handle* h, const double* theta_dev, int64_t B, int64_t ld, double* out_dev, int64_t ld_out, void* stream);
+/* Waits for the handle's device, returns the status bits raised since the last call (or -1) and clears them. */
+int32_t nmma_mm_status(nmma_mm_handle* h);
 
 int32_t nmma_em_profile_begin(nmma_em_handle* h, int32_t max_launches);
 int32_t nmma_em_profile_end(nmma_em_handle* h, double* fused_ms_total, double* combine_ms_total,

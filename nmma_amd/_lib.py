@@ -19,19 +19,19 @@ SRC_PATH = os.path.join(_HERE, "csrc", "em_kernels.hip")
 #: critical path).  Order = this machine's unit times, longest first (tools: _lib.UNIT_SECONDS after a forced build).
 SOURCES = ("em_kernels.hip", "em_lc64.hip", "em_lc.hip", "em_logl_w3.hip", "em_logl_w2.hip", "em_logl_wc1.hip", "em_logl_w1.hip", "em_logl_f5.hip", "em_logl_f02.hip",
            "em_logl_w4.hip", "em_logl_wc2.hip", "em_logl_w5.hip", "em_logl_f8.hip", "em_logl_f6.hip", "em_logl_f9.hip", "em_logl_f4.hip", "em_logl_f3.hip", "em_logl_f7.hip",
-           "gw_kernels.hip", "em_logl_f1.hip", "walk_kernels.hip", "em_mlp.hip", "em_gp.hip", "em_sc.hip", "em_bol.hip", "em_kn.hip", "em_pl.hip")
+           "gw_kernels.hip", "em_logl_f1.hip", "walk_kernels.hip", "em_mlp.hip", "em_gp.hip", "em_sc.hip", "em_bol.hip", "em_kn.hip", "em_pl.hip", "mm_convert.hip")
 #: per-unit flags after the common ones.  The EM unit keeps -ffp-contract=off (the reference's numpy expressions are not fused and
 #: the parity tests compare bit patterns of intermediate results); the GW unit has no bit-level counterpart (its reference
 #: arithmetic is third-party and absent) and lets hipcc fuse multiply-adds: a quarter fewer instructions in the bin loop.
-# The GP, shock-cooling, bolometric, kilonova-integrator and power-law units (fp64 only) are kept clear of packed-fp32 instruction selection.
+# The GP, shock-cooling, bolometric, kilonova-integrator, power-law and parameter-conversion units (fp64 only) are kept clear of packed-fp32 instruction selection.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"gw_kernels.hip": ["-ffp-contract=fast"], "em_gp.hip": _NO_PACKED_FP32, "em_mlp.hip": _NO_PACKED_FP32, "em_sc.hip": _NO_PACKED_FP32, "em_bol.hip": _NO_PACKED_FP32,
-              "em_kn.hip": _NO_PACKED_FP32, "em_pl.hip": _NO_PACKED_FP32}
+              "em_kn.hip": _NO_PACKED_FP32, "em_pl.hip": _NO_PACKED_FP32, "mm_convert.hip": _NO_PACKED_FP32}
 
 #: seconds each unit took in this process's last build_library call (tools: order SOURCES longest first)
 UNIT_SECONDS = {}
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 STACK2_GAP_FREE = 1
 STACK2_COMPLETED = 2
 MAX_PARAMS = 8
@@ -50,6 +50,14 @@ EXT_LINEAR, EXT_P92_SMC_HOST = range(2)
 BOL_SUPPLIED, BOL_ARNETT, BOL_ARNETT_MODIFIED = range(3)
 PL_SR2023, PL_SYNCHROTRON = range(2)
 PL_FUSED_MAX_NS = 256
+MM_CHIRP_MASS_RATIO, MM_COMPONENT_MASSES = range(2)
+MM_EOS_TABLES, MM_EOS_SINGLE, MM_EOS_QUR, MM_EOS_GIVEN = range(4)
+MM_JET_NONE, MM_JET_TOPHAT, MM_JET_POWERLAW = range(3)
+MM_SPIN_CHI, MM_SPIN_A_COS_TILT, MM_SPIN_A_TILT = range(3)
+#: the derived columns of nmma_mm_convert, in the order of ``nmma_mm_config::out_col``
+MM_OUTPUTS = ("log10_mej_dyn", "log10_mej_wind", "log10_mej", "log10_E0", "lambda_1", "lambda_2", "radius_1", "radius_2", "TOV_mass", "R_14", "R_16")
+MM_STATUS_EOS_RANGE = 1
+MM_MAX_NODES = 1024
 
 
 class NMMAHipError(RuntimeError):
@@ -140,6 +148,21 @@ class PlConfig(C.Structure):
         ("abi_version", C.c_int32), ("device", C.c_int32), ("kind", C.c_int32), ("n_filters", C.c_int32),
         ("alpha", Slot), ("beta", Slot), ("f_ref", Slot),
         ("amp_slots", C.POINTER(Slot)), ("floor_slots", C.POINTER(Slot)), ("residual_mag", _pd),
+    ]
+
+
+class MmConfig(C.Structure):
+    """Mirror of ``struct nmma_mm_config`` (field order must match the header)."""
+    _fields_ = [
+        ("abi_version", C.c_int32), ("device", C.c_int32), ("n_dim", C.c_int32), ("mass_mode", C.c_int32),
+        ("mass_a", Slot), ("mass_b", Slot),
+        ("redshift_mode", C.c_int32), ("redshift", Slot), ("luminosity_distance", Slot),
+        ("n_cosmo", C.c_int32), ("dist_grid", _pd), ("z_grid", _pd),
+        ("eos_mode", C.c_int32), ("n_eos", C.c_int32), ("eos_n_nodes", _pi), ("eos_radius", _pd), ("eos_mass", _pd), ("eos_log_lambda", _pd),
+        ("eos", Slot), ("lambda_1", Slot), ("lambda_2", Slot), ("tov_mass", Slot), ("radius_1", Slot), ("radius_2", Slot), ("r_16", Slot),
+        ("fits", C.c_int32), ("alpha", Slot), ("ratio_zeta", Slot), ("spin_mode", C.c_int32), ("spin_a", Slot), ("spin_b", Slot),
+        ("jet", C.c_int32), ("ratio_epsilon", Slot), ("theta_core", Slot), ("wing", Slot), ("wing_is_angle", C.c_int32), ("b", Slot),
+        ("out_col", C.c_int32 * len(MM_OUTPUTS)),
     ]
 
 
@@ -275,6 +298,10 @@ PROTOTYPES = {
     "nmma_pl_model_lightcurves": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nmma_pl_loglike": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "nmma_pl_fused": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "nmma_mm_create": (C.c_int32, [C.POINTER(MmConfig), C.POINTER(C.c_void_p)]),
+    "nmma_mm_destroy": (None, [C.c_void_p]),
+    "nmma_mm_convert": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "nmma_mm_status": (C.c_int32, [C.c_void_p]),
     "nmma_em_loglike_lc_parts": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nmma_em_lightcurves_lc": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nmma_em_check": (C.c_int32, [C.c_void_p]),

@@ -311,8 +311,8 @@ class MultimessengerConversion:
     """``nmma/core/conversion.py:768-824``: the ordered chain of parameter conversions a joint likelihood applies -- cosmology
     (distance from redshift / Hubble constant), GW source frame, EOS, kilonova ejecta fits, EM, custom -- each a callable
     ``parameters -> parameters``.  The container, its ordering and ``convert_to_multimessenger_parameters`` are the reference's;
-    the EOS converter and ``KilonovaEjectaFitting`` (NR fit formulae over EOS tables, SURVEY section 2: out of scope) are not
-    built here, so ``'ejecta'`` needs the callable itself (``{'ejecta': my_fit}``) instead of ``True``.  Works on scalars (one
+    ``'eos'`` and ``'ejecta'`` take the callables themselves -- :class:`EOSTableConverter` and :class:`KilonovaEjectaFitting` below run
+    on the device (``{'ejecta': KilonovaEjectaFitting()}``); ``True`` is refused.  Works on scalars (one
     sample) and on arrays (the batched constraint check of ``MultiMessengerLikelihood.log_likelihood_batch``)."""
 
     def __init__(self, *conversions):
@@ -379,3 +379,191 @@ class MultimessengerConversion:
 
     def identity_conversion(self, parameters):
         return parameters
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# EOS look-up and kilonova ejecta fits on the device (reference :222-270, :318-766; nmma/eos/eos_processing.py:292-360).
+# The two callables below have the reference's call shape (parameters -> parameters) and run kernel mm_convert
+# (csrc/mm_convert.hip) through nmma_amd.engine.MMConvertEngine; a MultiMessengerLikelihood whose chain holds them keeps
+# the whole batch on the device.
+# ---------------------------------------------------------------------------------------------------------------------
+EJECTA_KEYS = ("log10_mej_dyn", "log10_mej_wind", "log10_mej", "log10_E0")
+EOS_KEYS = ("lambda_1", "lambda_2", "radius_1", "radius_2", "TOV_mass", "R_14", "R_16")
+
+
+def load_eos_files(eos_dir, n_eos=None):
+    """The reference's EOS files ``{i+1}.dat`` (columns radius [km], mass [Msun], lambda) as a list of (radius, mass, lambda)."""
+    import os
+    if n_eos is None:
+        n_eos = len([f for f in os.listdir(eos_dir) if f.endswith(".dat")])
+    return [tuple(np.loadtxt(os.path.join(eos_dir, f"{j + 1}.dat"), usecols=[0, 1, 2]).T) for j in range(n_eos)]
+
+
+def plan_mm_conversion(names, fixed=None, eos_tables=None, cosmo_grid=None, fits=True):
+    """What kernel mm_convert does for sampled columns ``names`` and fixed values ``fixed``: a dict with the modes, the key every
+    input slot reads (``slots``: key or (key, default)) and ``derived``, the keys written behind the sampled columns.  A derived key
+    that is itself sampled or fixed is NOT in ``derived``: "we always prefer explicitly sampled ejecta parameters" (:326).  Pure
+    Python: the argument checks run without a device."""
+    from .. import _lib as L
+    names, fixed = list(names), dict(fixed or {})
+    have = set(names) | set(fixed)
+    plan = dict(names=names, fixed=fixed, fits=bool(fits), slots={})
+
+    def need(*keys, why):
+        missing = [k for k in keys if k not in have]
+        if missing:
+            raise KeyError(f"{why} needs {missing}: neither sampled nor fixed (sampled: {names}, fixed: {sorted(fixed)})")
+
+    # ---- masses and their frame
+    if {"mass_1_source", "mass_2_source"} <= have:
+        plan.update(mass_mode=L.MM_COMPONENT_MASSES, redshift_mode=L.Z_ZERO)
+        plan["slots"].update(mass_a="mass_1_source", mass_b="mass_2_source")
+    else:
+        if {"chirp_mass", "mass_ratio"} <= have:
+            plan["mass_mode"] = L.MM_CHIRP_MASS_RATIO
+            plan["slots"].update(mass_a="chirp_mass", mass_b="mass_ratio")
+        elif {"mass_1", "mass_2"} <= have:
+            plan["mass_mode"] = L.MM_COMPONENT_MASSES
+            plan["slots"].update(mass_a="mass_1", mass_b="mass_2")
+        else:
+            raise KeyError("the conversion needs (chirp_mass, mass_ratio), (mass_1, mass_2) or (mass_1_source, mass_2_source); "
+                           f"sampled: {names}, fixed: {sorted(fixed)}")
+        if "redshift" in have:
+            plan["redshift_mode"] = L.Z_SLOT
+            plan["slots"]["redshift"] = "redshift"
+        elif "luminosity_distance" in have:
+            if cosmo_grid is None:
+                raise ValueError("source-frame masses from a luminosity distance need the z(d_L) grid: pass cosmo_grid")
+            plan["redshift_mode"] = L.Z_GRID
+            plan["slots"]["luminosity_distance"] = "luminosity_distance"
+        else:
+            raise KeyError("source-frame masses need 'redshift' or 'luminosity_distance'")
+    # ---- the EOS step
+    produced = []
+    if eos_tables is not None:
+        if "EOS" in have:
+            plan["eos_mode"] = L.MM_EOS_TABLES
+            plan["slots"]["eos"] = "EOS"
+        elif len(eos_tables) == 1:
+            plan["eos_mode"] = L.MM_EOS_SINGLE
+        else:
+            raise KeyError(f"{len(eos_tables)} EOS tables and no sampled or fixed 'EOS' index")
+        produced += list(EOS_KEYS)
+    elif {"lambda_1", "lambda_2"} <= have and not {"radius_1", "radius_2"} <= have:
+        plan["eos_mode"] = L.MM_EOS_QUR
+        plan["slots"].update(lambda_1="lambda_1", lambda_2="lambda_2", tov_mass=("TOV_mass", np.nan))
+        if fits:
+            need("TOV_mass", why="the disk-mass fit behind the quasi-universal relations")
+        produced += ["radius_1", "radius_2", "R_16"]
+    else:
+        need("radius_1", "radius_2", "TOV_mass", "R_16", why="the ejecta fits without an EOS step")
+        plan["eos_mode"] = L.MM_EOS_GIVEN
+        plan["slots"].update(radius_1="radius_1", radius_2="radius_2", tov_mass="TOV_mass", r_16="R_16")
+    # ---- the fits and the jet
+    plan["jet"], plan["spin_mode"], plan["wing_is_angle"] = L.MM_JET_NONE, L.MM_SPIN_CHI, 0
+    if fits:
+        need("alpha", "ratio_zeta", why="KilonovaEjectaFitting")
+        plan["slots"].update(alpha="alpha", ratio_zeta="ratio_zeta")
+        if "chi_1" in have:
+            plan["slots"]["spin_a"] = "chi_1"
+        elif "a_1" in have and ("cos_tilt_1" in have or "tilt_1" in have):
+            cos = "cos_tilt_1" in have
+            plan["spin_mode"] = L.MM_SPIN_A_COS_TILT if cos else L.MM_SPIN_A_TILT
+            plan["slots"].update(spin_a="a_1", spin_b="cos_tilt_1" if cos else "tilt_1")
+        else:
+            # (the reference raises KeyError when its NSBH branch finds no spin; here such a row's masses are NaN and the row floors)
+            plan["slots"]["spin_a"] = ("chi_1", np.nan)
+        produced = list(EJECTA_KEYS[:3]) + produced
+        if "log10_E0" not in have:
+            wing = [k for k in ("alphaWing", "thetaWing") if k in have]
+            if "b" in have:
+                if not wing:
+                    raise KeyError("a power-law jet ('b') needs 'alphaWing' or 'thetaWing'")
+                if wing[0] == "thetaWing":
+                    need("thetaCore", why="alphaWing = thetaWing / thetaCore")
+                plan.update(jet=L.MM_JET_POWERLAW, wing_is_angle=int(wing[0] == "thetaWing"))
+                plan["slots"].update(wing=wing[0], b="b")
+            elif wing:
+                raise NotImplementedError(
+                    f"a Gaussian jet ({wing[0]!r} without 'b') is not evaluated on the device: its energy needs erf of a complex argument "
+                    "(reference :274-296), for which the device has no routine.  Sample 'b' (power-law jet) or drop the wing.")
+            else:
+                plan["jet"] = L.MM_JET_TOPHAT
+            plan["slots"].update(ratio_epsilon=("ratio_epsilon", 2e-4), theta_core=("thetaCore", 0.105))
+            produced.insert(3, "log10_E0")
+    plan["derived"] = [k for k in L.MM_OUTPUTS if k in produced and k not in have]
+    return plan
+
+
+class _DeviceConversion:
+    """Shared call shape: a dict of numpy scalars / arrays or of CUDA tensors in, the same container out with the derived keys added."""
+
+    eos_tables, cosmo_grid, fits, device = None, None, True, 0
+
+    def _engine(self, names, fixed):
+        from ..engine import MMConvertEngine
+        key = (tuple(names), tuple(sorted(fixed.items())))
+        if getattr(self, "_engine_key", None) != key:
+            self._eng = MMConvertEngine(names, fixed, eos_tables=self.eos_tables, cosmo_grid=self.cosmo_grid, fits=self.fits, device=self.device)
+            self._engine_key = key
+        return self._eng
+
+    def __call__(self, parameters):
+        if _symbolic(*parameters.values()):
+            from .constraints import opaque_like
+            for key in EJECTA_KEYS + EOS_KEYS:
+                parameters.setdefault(key, opaque_like(None))
+            return parameters
+        import torch
+        numeric = {k: v for k, v in parameters.items() if isinstance(v, torch.Tensor) or np.asarray(v).dtype.kind in "fiu"}
+        tensors = any(isinstance(v, torch.Tensor) for v in numeric.values())
+        cols = {k: v for k, v in numeric.items() if (v.dim() if isinstance(v, torch.Tensor) else np.ndim(v)) > 0}
+        fixed = {k: float(v) for k, v in numeric.items() if k not in cols}
+        names = list(cols) or [next(iter(fixed))]
+        scalar = not cols
+        if scalar:
+            cols = {names[0]: np.array([fixed.pop(names[0])])}
+        if tensors:
+            theta = torch.stack([torch.as_tensor(cols[k]).to(f"cuda:{self.device}", torch.float64).reshape(-1) for k in names], dim=1)
+        else:
+            theta = np.column_stack([np.asarray(cols[k], dtype=float).reshape(-1) for k in names])
+        eng = self._engine(names, fixed)
+        out = eng.convert(theta)
+        for j, key in enumerate(eng.derived_names):
+            col = out[:, len(names) + j]
+            parameters[key] = col if not scalar else float(col[0])
+        return parameters
+
+
+class EOSTableConverter(_DeviceConversion):
+    """``EoSConverter(method="tabulated")`` on the device: per row the ``EOS``-th table (or the only one) gives lambda_1, lambda_2,
+    radius_1, radius_2 at the source-frame masses and TOV_mass, R_14, R_16.  ``eos_tables``: a list of (radius, mass, lambda) arrays;
+    ``eos_dir``: a directory of the reference's ``{i+1}.dat`` files.  Pass it as ``'eos'`` of a ``MultimessengerConversion``."""
+
+    fits = False
+
+    def __init__(self, eos_tables=None, eos_dir=None, n_eos=None, cosmo_grid=None, device=0):
+        if (eos_tables is None) == (eos_dir is None):
+            raise ValueError("EOSTableConverter takes eos_tables or eos_dir")
+        tables = load_eos_files(eos_dir, n_eos) if eos_tables is None else eos_tables
+        self.eos_tables = [tuple(np.asarray(a, dtype=float) for a in t) for t in tables]
+        for e, (radius, mass, lam) in enumerate(self.eos_tables):
+            if not (radius.ndim == mass.ndim == lam.ndim == 1 and len(radius) == len(mass) == len(lam) >= 2):
+                raise ValueError(f"EOS {e}: radius, mass and lambda must be 1-D arrays of one length >= 2")
+            if not np.all(np.diff(mass) > 0):
+                # (np.interp is undefined there: the reference would answer garbage silently)
+                raise ValueError(f"EOS {e}: the masses are not strictly ascending (node {int(np.argmax(np.diff(mass) <= 0)) + 1}); "
+                                 "cut the table at its maximum mass")
+            if not np.all(lam > 0):
+                raise ValueError(f"EOS {e}: tidal deformabilities must be positive (the look-up interpolates log lambda)")
+        self.cosmo_grid, self.device = cosmo_grid, int(device)
+
+
+class KilonovaEjectaFitting(_DeviceConversion):
+    """``KilonovaEjectaFitting`` (reference :744-766) on the device: the BNS fits, the NSBH fits, the BBH case and log10_E0 from the
+    disk mass (top-hat or power-law jet), per row by the branch the reference's array form takes.  Called on its own it reads
+    radius_1, radius_2, TOV_mass, R_16 (or lambda_1, lambda_2 for the quasi-universal relations) from ``parameters``; behind an
+    :class:`EOSTableConverter` in a ``MultiMessengerLikelihood`` chain the two are one launch."""
+
+    def __init__(self, cosmo_grid=None, device=0):
+        self.cosmo_grid, self.device = cosmo_grid, int(device)

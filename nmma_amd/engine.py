@@ -1028,3 +1028,87 @@ class BolometricEngine:
             self.close()
         except Exception:
             pass
+
+
+class MMConvertEngine:
+    """Owns one ``nmma_mm_handle``: sampled binary and EOS parameters -> the surrogate's inputs in one launch (kernel ``mm_convert``:
+    source-frame masses, tabulated-EOS look-up or quasi-universal relations, kilonova ejecta fits, log10_E0).
+
+    Parameters
+    ----------
+    parameter_names : list[str]   columns of ``theta``
+    fixed : dict                  fixed parameters
+    eos_tables : list of (radius, mass, lambda) arrays, or None (quasi-universal relations / radii given as parameters)
+    cosmo_grid : (dist_grid, z_grid), used when the masses are detector-frame and no ``redshift`` is sampled or fixed
+    fits : run the ejecta fits (False: the EOS step alone)
+
+    ``convert(theta)`` returns ``[B, D + k]``: the sampled columns, then ``derived_names``; ``names_out`` lists all of them.
+    """
+
+    def __init__(self, parameter_names, fixed=None, eos_tables=None, cosmo_grid=None, fits=True, device=0):
+        from .core.conversion import plan_mm_conversion
+        self._handle = None
+        plan = plan_mm_conversion(parameter_names, fixed, eos_tables, cosmo_grid, fits)
+        self._lib = lib = L.load_library()
+        names, fixed = plan["names"], plan["fixed"]
+        self.parameter_names, self.device, self.plan = names, int(device), plan
+        self.derived_names = list(plan["derived"])
+        self.names_out = names + self.derived_names
+        cfg = L.MmConfig()
+        cfg.abi_version, cfg.device, cfg.n_dim = L.ABI_VERSION, self.device, len(names)
+        for field in ("mass_mode", "redshift_mode", "eos_mode", "jet", "spin_mode", "wing_is_angle"):
+            setattr(cfg, field, plan[field])
+        cfg.fits = int(plan["fits"])
+        for field, key in plan["slots"].items():
+            key, default = key if isinstance(key, tuple) else (key, None)
+            setattr(cfg, field, _plain_slot(key, names, fixed, default))
+        keep = []
+        if plan["redshift_mode"] == L.Z_GRID:
+            dg, zg = _f64(cosmo_grid[0]), _f64(cosmo_grid[1])
+            keep += [dg, zg]
+            cfg.n_cosmo, cfg.dist_grid, cfg.z_grid = len(dg), _ptr(dg, C.c_double), _ptr(zg, C.c_double)
+        if eos_tables is not None:
+            n_nodes = _i32([len(t[1]) for t in eos_tables])
+            radius, mass = (_f64(np.concatenate([np.asarray(t[j], dtype=float) for t in eos_tables])) for j in (0, 1))
+            lam = np.concatenate([np.asarray(t[2], dtype=float) for t in eos_tables])
+            if not np.all(lam > 0):
+                raise L.NMMAHipError("EOS tables: tidal deformabilities must be positive (the look-up interpolates log lambda)")
+            log_lam = _f64(np.log(lam))              # numpy's log: the reference interpolates np.log(lambdas)
+            keep += [n_nodes, radius, mass, log_lam]
+            cfg.n_eos, cfg.eos_n_nodes = len(eos_tables), _ptr(n_nodes, C.c_int32)
+            cfg.eos_radius, cfg.eos_mass, cfg.eos_log_lambda = (_ptr(a, C.c_double) for a in (radius, mass, log_lam))
+        for k, key in enumerate(L.MM_OUTPUTS):
+            cfg.out_col[k] = len(names) + self.derived_names.index(key) if key in self.derived_names else -1
+        handle = C.c_void_p()
+        L.check(lib.nmma_mm_create(C.byref(cfg), C.byref(handle)), "nmma_mm_create")
+        self._handle = handle
+
+    _dev_theta = EMEngine._dev_theta
+    _stream = EMEngine._stream
+
+    def convert(self, theta, stream=None):
+        """``[B, D]`` -> ``[B, D + k]`` (columns ``names_out``): torch CUDA tensor in -> tensor out (asynchronous), numpy in -> numpy out."""
+        import torch
+        t = self._dev_theta(theta)
+        out = torch.empty((t.shape[0], len(self.names_out)), dtype=torch.float64, device=t.device)
+        L.check(self._lib.nmma_mm_convert(self._handle, C.c_void_p(t.data_ptr()), t.shape[0], t.stride(0), C.c_void_p(out.data_ptr()),
+                                          out.stride(0), self._stream(stream)), "nmma_mm_convert")
+        return out if isinstance(theta, torch.Tensor) else out.cpu().numpy()
+
+    def status(self):
+        """Bits raised since the last call (``_lib.MM_STATUS_EOS_RANGE``: a row's EOS index was out of range and the row was floored)."""
+        bits = self._lib.nmma_mm_status(self._handle)
+        if bits < 0:
+            raise L.NMMAHipError("nmma_mm_status failed")
+        return bits
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._lib.nmma_mm_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

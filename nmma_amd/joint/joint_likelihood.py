@@ -141,6 +141,11 @@ class MultiMessengerLikelihood(NMMALikelihoodMixin, _BilbyLikelihood):
         external_logl = external_logl or {}
         as_torch = isinstance(theta, torch.Tensor)
         parts, dev = [], None
+        sampled_theta, sampled_names = theta, names
+        converter = self.device_converter(names)
+        if converter is not None:
+            # the chain's EOS look-up and ejecta fits in ONE launch: the messengers read the derived columns behind the sampled ones
+            theta, names = converter.convert(theta), converter.names_out
         for lh in self.likelihoods:
             if isinstance(lh, ExternalLogLikelihood):
                 if lh.name not in external_logl:
@@ -168,8 +173,36 @@ class MultiMessengerLikelihood(NMMALikelihoodMixin, _BilbyLikelihood):
                                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
                     "nmma_logl_sum_floor")
         if self.constraints:
-            total = self._apply_joint_constraints(total, theta, names)
+            total = self._apply_joint_constraints(total, sampled_theta, sampled_names)
         return total if as_torch else total.cpu().numpy()
+
+    def device_converter(self, names=None):
+        """The ``MMConvertEngine`` of this likelihood's chain for sampled columns ``names``, or None when the chain holds neither an
+        ``EOSTableConverter`` nor a ``KilonovaEjectaFitting`` (any other callable under ``'eos'`` / ``'ejecta'`` keeps the messengers
+        on the sampled columns).  The z(d_L) grid is the converters' own, else the EM messenger's."""
+        if self.multi_conversion is None:
+            return None
+        from ..core.base import fixed_value, is_constraint
+        from ..core.conversion import EOSTableConverter, KilonovaEjectaFitting
+        chain = self.multi_conversion._conversions
+        eos = next((c for c in chain if isinstance(c, EOSTableConverter)), None)
+        fit = next((c for c in chain if isinstance(c, KilonovaEjectaFitting)), None)
+        if eos is None and fit is None:
+            return None
+        if names is None:
+            names = [k for k, p in self.priors.items() if fixed_value(p) is None and not is_constraint(p)]
+        names = list(names)
+        if getattr(self, "_converter_names", None) != names:
+            from ..engine import MMConvertEngine
+            fixed = {k: fixed_value(p) for k, p in self.priors.items() if fixed_value(p) is not None and k not in names}
+            grids = [getattr(c, "cosmo_grid", None) for c in (eos, fit)]
+            grids += [getattr(getattr(getattr(lh, "sub_model", None), "light_curve_model", None), "cosmo_grid", None) for lh in self.likelihoods]
+            grid = next((g for g in grids if g is not None), None)
+            device = (eos or fit).device
+            self._converter = MMConvertEngine(names, fixed, eos_tables=eos.eos_tables if eos is not None else None, cosmo_grid=grid,
+                                              fits=fit is not None, device=device)
+            self._converter_names = names
+        return self._converter
 
     def _apply_joint_constraints(self, total, theta, names):
         """The joint prior's Constraint entries on the batch: on the device when ``theta`` is a CUDA tensor and every constrained
